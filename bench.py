@@ -5,7 +5,23 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-One JSON line on rank 0.  A "step" is one pass of the hot path over one synthetic minibatch of
+One JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps (one region), writes the outputs
+of the last timed step if `--dump-outputs DIR` is given and prints the line: `value` (images/s) and `ms_per_step` of
+those steps, `config` and `memory`.  Everything else below -- the other launch mode, the library-fp32 child run,
+three timed regions, `roofline` (event timing, micro-benchmark, in-model replay, copy ceiling, committed profiles),
+`accuracy` and `cpu_baseline` -- runs only under `--full`.
+
+`--dump-outputs DIR` (rank 0): what the last timed step handed back, for output-for-output comparison of two builds
+on the same seeded inputs -- `DIR/<loss name>.npy` for every entry of the loss dict `ZiraTrainer.run_step` returns,
+and `DIR/side_branch_params.npy`, the trainable side-branch tensors as that step's AdamW update left them (one flat
+float32 vector in the trainer's parameter order; a fixed, seeded sample of it if it exceeded 48 MB).  The inputs
+(model initialisation, minibatches) are the same in every run with the same arguments, and in practice so are the
+outputs: the step has no order-dependent fp32 accumulation (the decoder's MSDA backward sums in double and rounds once;
+a run-to-run difference would need a last-bit difference of a double sum to land on an fp32 rounding boundary).  A
+last-bit difference in one step's gradients does not stay small: the discrete query selection and matching of later
+steps amplify it to percent-level loss differences.
+
+A "step" is one pass of the hot path over one synthetic minibatch of
 `--batch` (default 2) uint8 800x1333 images per GPU, i.e. BASELINE.json configs[1] per rank:
 frozen Swin-T + BERT-base front end (random init -- no checkpoint offline), both ZiRa side
 branches (fused RSB epilogue kernels), 6 encoder + 6 decoder layers with 12 MSDA forward and
@@ -555,6 +571,24 @@ def profile_kernel_times():
     return avg, os.path.relpath(files[-1], ROOT)
 
 
+DUMP_PARAM_BYTES = 48 << 20   # side_branch_params.npy at most (the whole dump stays under 64 MB)
+
+
+def dump_outputs(dirname, losses, params):
+    """`--dump-outputs DIR`: the loss dict of the last timed step and the trainable side-branch parameters as its AdamW
+    update left them (one flat float32 vector in the trainer's order; a sorted sample of fixed seed beyond 48 MB)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in losses.items():
+        np.save(os.path.join(dirname, name + ".npy"), v.detach().float().cpu().numpy())
+    flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+    if flat.numel() * 4 > DUMP_PARAM_BYTES:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(flat.numel(), generator=g)[:DUMP_PARAM_BYTES // 4].sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(dirname, "side_branch_params.npy"), flat.cpu().numpy())
+
+
 def summarize_timing(records, B_expect):
     """Group the (kind, dims, e0, e1) records of `_C.TIMING` -> {group: (calls, avg seconds, dims)}."""
     groups = {}
@@ -587,8 +621,13 @@ def main():
                     help="do not queue the frozen front end (Swin + BERT) of the next minibatch on a second stream "
                          "while the current step runs (same work per step either way)")
     ap.set_defaults(prefetch=True)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: the other launch mode, the library-fp32 child run, "
+                         "three timed regions, roofline, accuracy and cpu_baseline (each of them still subject to its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (loss dict entries, side-branch parameters)")
     ap.add_argument("--kernel-timing-steps", type=int, default=4,
-                    help="eager steps after the timed region with HIP events around every MSDA call (roofline.kernels)")
+                    help="--full: eager steps after the timed region with HIP events around every MSDA call (roofline.kernels)")
     ap.add_argument("--cpu-sample-div", type=int, default=1,
                     help="cpu_baseline runs one step on an image with sides divided by this")
     ap.add_argument("--backbone", default="swin_T_224_1k",
@@ -603,9 +642,10 @@ def main():
     ap.add_argument("--force-collectives", action="store_true",
                     help="with WORLD_SIZE=1 under torch.distributed.run: still create the nccl group and issue every barrier / "
                          "all-reduce of the N > 1 path (a hardware check of that path on a 1-GPU box)")
-    ap.add_argument("--regions", type=int, default=3,
-                    help="timed regions of --steps steps per launch mode; the line reports the MEDIAN region (each region is "
-                         "bracketed by barrier + synchronize on both sides; all of them are listed in config.launch_modes)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps per launch mode (default 1; 3 with --full); the line reports the MEDIAN "
+                         "region (each region is bracketed by barrier + synchronize on both sides; all of them are listed in "
+                         "config.launch_modes)")
     ap.add_argument("--no-gemm-arith-mode", action="store_true",
                     help="skip the extra timed regions with the frozen products in the library's plain fp32 GEMMs (a child "
                          "process, reported beside the headline in config.gemm_arith)")
@@ -620,6 +660,8 @@ def main():
     ap.add_argument("--no-second-mode", action="store_true",
                     help="skip the second timed region in the other launch mode (eager <-> hipGraph replay)")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 3 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus, sys.argv[1:])  # does not return
@@ -635,7 +677,7 @@ def main():
     # slower whatever it is (scripts/ab_step.py's note; round 5: 36.5 ms in-process against 32.2 ms alone), and a process that
     # has initialised the GPU must not start programs on this pool.  One GPU, the flagship configuration, fp32 only.
     arith_child = None
-    if (world == 1 and "WORLD_SIZE" not in os.environ and not args.no_gemm_arith_mode and args.dtype == "f32"
+    if (args.full and world == 1 and "WORLD_SIZE" not in os.environ and not args.no_gemm_arith_mode and args.dtype == "f32"
             and args.backbone == "swin_T_224_1k" and args.gemm_arith != "f32"):
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--gemm-arith", "f32", "--no-gemm-arith-mode", "--no-second-mode",
@@ -696,13 +738,14 @@ def main():
                                seed=rank * 1009 + i, device=dev) for i in range(max(1, args.minibatches))]
     data = batches[0]
     cursor = [0]
+    last_losses = {}
 
     def run_steps(n):
         for _ in range(n):
             cur = batches[cursor[0] % len(batches)]
             nxt = batches[(cursor[0] + 1) % len(batches)]
             cursor[0] += 1
-            trainer.run_step(cur, next_data=nxt if args.prefetch else None)
+            last_losses["step"] = trainer.run_step(cur, next_data=nxt if args.prefetch else None)
 
     def timed(n):
         torch.cuda.synchronize()
@@ -733,10 +776,12 @@ def main():
         trainer.flat_grad.zero_()
         run_steps(args.warmup)
     regions = max(1, args.regions)
-    _C.TIMING = []
+    _C.TIMING = [] if args.full else None
     all_regions = {"graph" if args.transformer_graph else "eager": [timed(args.steps) for _ in range(regions)]}
-    records, _C.TIMING = _C.TIMING, None
-    if not args.no_second_mode and args.dtype == "f32":   # the same steps in the other launch mode (every rank: collectives)
+    records, _C.TIMING = _C.TIMING or [], None
+    if args.dump_outputs and rank == 0:   # (before any later step can overwrite the graphs' outputs or the parameters)
+        dump_outputs(args.dump_outputs, last_losses["step"], trainer.params)
+    if args.full and not args.no_second_mode and args.dtype == "f32":   # the same steps in the other launch mode (every rank: collectives)
         other = not args.transformer_graph
         model.use_transformer_graph = other
         try:
@@ -758,7 +803,7 @@ def main():
         except (KeyError, TypeError):
             pass
     timing_source = "HIP events around every native MSDA call of the timed steps"
-    if args.transformer_graph and args.kernel_timing_steps > 0:   # (every rank: the steps hold collectives)
+    if args.full and args.transformer_graph and args.kernel_timing_steps > 0:   # (every rank: the steps hold collectives)
         # graph replays hide the launches from event timing: the same step, launched eagerly, right after
         model.use_transformer_graph = False
         trainer.run_step(data)          # (no prefetch here: a concurrent Swin would sit inside the event brackets)
@@ -773,7 +818,8 @@ def main():
                          "region (its steps replay the transformer from hipGraphs, which hides the launches)"
                          % args.kernel_timing_steps)
     replay = None
-    if not args.no_micro:
+    micro = args.full and not args.no_micro
+    if micro:
         got = capture_inmodel(trainer, data)     # (a training step: every rank, the collectives inside need them all)
         if rank == 0:
             replay = inmodel_replay(got, dev)
@@ -818,7 +864,7 @@ def main():
                             "frac": nbytes / avg_s / 1e9 / HBM_PEAK_GBS,
                             "share_of_step": (calls / timed_steps) * avg_s / (elapsed / args.steps),
                             "dims_BSMDLQP": list(dims)}
-        prof_avg, prof_file = profile_kernel_times()
+        prof_avg, prof_file = profile_kernel_times() if args.full else ({}, None)
         for key, names in PROFILE_GROUPS.items():   # the same groups from the committed rocprofv3 summary of this command
             if key in kernels and all(n in prof_avg for n in names[:1]):
                 us = sum(prof_avg.get(n, 0.0) for n in names)
@@ -828,7 +874,7 @@ def main():
         dominant = max(kernels, key=lambda k: kernels[k]["share_of_step"]) if kernels else None
         roofline = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None,
                     "kernels": kernels, "dominant": dominant, "timing_source": timing_source}
-        pmc = pmc_traffic()
+        pmc = pmc_traffic() if args.full else None
         if pmc:
             for key, nbytes in pmc.pop("groups", {}).items():   # HBM bytes per launch of every group (PMC, uniform / grid inputs)
                 if key in kernels:
@@ -842,7 +888,7 @@ def main():
                                        "B=%d,S=%d,M=%d,D=%d,L=%d,Q=%d,P=%d" % tuple(f["dims_BSMDLQP"]),
                              "achieved": nbytes / t_pair / 1e9, "frac": nbytes / t_pair / 1e9 / HBM_PEAK_GBS,
                              "algorithmic_bytes": nbytes, "avg_us": t_pair * 1e6})
-        if not args.no_micro:
+        if micro:
             roofline["micro"] = msda_micro(dev)
         if replay:
             roofline["inmodel_replay"] = replay
@@ -866,7 +912,7 @@ def main():
                                                 "warm_replay = the same calls back to back (round 3's headline); "
                                                 "eager_events = " + timing_source})
         # what a plain streaming kernel moves on this box, and the headline against it
-        if not args.no_micro:
+        if micro:
             try:
                 roofline["copy_ceiling"] = copy_ceiling(dev)
                 if roofline.get("achieved"):
@@ -876,7 +922,7 @@ def main():
         images = args.steps * args.batch * world
         flagship = args.backbone == "swin_T_224_1k" and args.dtype == "f32"
         accuracy = None
-        if flagship and world == 1 and not args.no_accuracy and args.gemm_arith != "f32":
+        if args.full and flagship and world == 1 and not args.no_accuracy and args.gemm_arith != "f32":
             try:
                 accuracy = arithmetic_accuracy(dev)
             except RuntimeError as e:
@@ -925,8 +971,8 @@ def main():
                 "launch_modes": {k: {"images_per_s": images / v, "ms_per_step": v / args.steps * 1e3,
                                      "regions_ms_per_step": [x / args.steps * 1e3 for x in all_regions[k]]}
                                  for k, v in sorted(modes.items())},
-                "value_is": "median of %d timed regions of %d steps in the configured launch mode (%s)"
-                            % (regions, args.steps, primary_mode)
+                "value_is": ("median of %d timed regions" % regions if regions > 1 else "one timed region")
+                            + " of %d steps in the configured launch mode (%s)" % (args.steps, primary_mode)
                             + ("; arithmetic of the frozen products: %s (%s)" % (
                                 args.gemm_arith, "the package's configured default, transformer.Switches.gemm_arith"
                                 if arith_is_default else "NOT the package default: started with --gemm-arith")),
@@ -952,12 +998,12 @@ def main():
                 "ranks_pinned_to_numa_cores": bool(pinned),
                 "msda_kernel_variant": _lib.variant_f32(32),
             },
-            "roofline": roofline,
+            **({"roofline": roofline} if args.full else {}),
             "memory": mem,
         }
         if accuracy is not None:
             line["accuracy"] = accuracy
-        if world == 1 and not args.no_cpu_baseline and flagship:
+        if args.full and world == 1 and not args.no_cpu_baseline and flagship:
             n_img, el, cores, desc = cpu_baseline_step(args.height, args.width, args.cpu_sample_div)
             line["cpu_baseline"] = {"value": n_img / el, "unit": "images/s", "cores": cores,
                                     "cores_on_host": os.cpu_count(), "kind": "port", "sample": desc, "msda": cpu_baseline_msda(cores)}

@@ -107,12 +107,13 @@ int zira_msda_bwd_f32_ws(const float *grad_out, const float *value, const int64_
  *                             tile in LDS (the only load that depends on a record is the query's grad_out row) while
  *                             forward-style waves -- one per (b, q, m) -- gather the value rows again and form
  *                             grad_sampling_loc / grad_attn_weight.  The shares of a split tile meet INSIDE that launch
- *                             (since round 5; there is no fold launch): each share writes its partial tile through to
- *                             memory and draws a ticket from the tile's agent-scope counter, and the share that arrives
- *                             last adds all of them in share order.  `plan` must come from zira_msda_*plan_f32 for the
+ *                             (since round 5; there is no fold launch): each share writes its partial tile -- its sums
+ *                             in double, unrounded -- through to memory and draws a ticket from the tile's agent-scope
+ *                             counter, and the share that arrives last adds all of them in share order and rounds to
+ *                             fp32 once.  `plan` must come from zira_msda_*plan_f32 for the
  *                             same dimensions, level tables, sampling_loc AND attn_weight.  Same outputs / contract as
  *                             zira_msda_bwd_f32_ws; deterministic apart from the order of the LDS sums in double (no fp32
- *                             atomics anywhere).
+ *                             atomics anywhere): in practice the result repeats from run to run.
  * The plan buffer needs no initialisation and 16-byte alignment; the backward uses regions of it as scratch (the partial
  * tiles and their tickets: hence `plan` is not const there).  A plan is NOT REENTRANT: it may serve several backward calls one
  * after the other on a stream, never two at the same time (they would race on the tickets and the partial tiles).  Limits of the planned path (zira_msda_plan_bytes returns 0 beyond them and the callers take

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in "${@:-default}"; do
   if [ "$lib" = default ]; then unset ZIRA_MSDA_LIB; else export ZIRA_MSDA_LIB=$root/build_ab/$lib.so; fi
   rm -rf /tmp/im
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/im -- python3 $root/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-micro --no-second-mode > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/im -- python3 $root/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-micro --no-second-mode > /dev/null 2>&1
   echo "== $lib"
   python3 - <<'PY'
 import csv, glob, re

@@ -6,7 +6,7 @@ tag=$1; shift
 out=$root/gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/trace_$tag -- python3 $root/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-micro --no-gemm-arith-mode --no-accuracy "$@" > $out/${tag}_bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/trace_$tag -- python3 $root/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-micro --no-gemm-arith-mode --no-accuracy "$@" > $out/${tag}_bench_under_rocprof.log 2>&1
 python3 - "$out" "$tag" "$*" <<'PY'
 import csv, glob, sys, re
 out, tag, flags = sys.argv[1:4]
@@ -16,7 +16,7 @@ for f in glob.glob("/tmp/trace_%s/**/*kernel_stats.csv" % tag, recursive=True):
 rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 with open("%s/%s_bench_kernel_stats.txt" % (out, tag), "w") as fh:
-    fh.write("rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-micro --no-gemm-arith-mode --no-accuracy %s\n" % flags)
+    fh.write("rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-micro --no-gemm-arith-mode --no-accuracy %s\n" % flags)
     fh.write("total kernel time %.1f ms over %d kernel names (3 warm-up steps, 3 timed regions of 10 steps in the configured launch mode and as many in the other one, the capture of\n"
              "the graphs -- 3 warm-up passes and one capture pass per piece -- and 1 + 4 eager steps for the MSDA event timing)\n" % (tot / 1e6, len(rows)))
     fh.write("%7s %11s %8s %12s  %s\n" % ("share", "total_ms", "calls", "avg_us", "kernel"))

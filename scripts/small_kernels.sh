@@ -5,7 +5,7 @@ out=/tmp/kt_small
 max=${1:-20}; shift
 cd /tmp && export TMPDIR=/tmp
 rm -rf $out
-rocprofv3 --kernel-trace --output-format csv -d $out -- python3 $root/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-micro "$@" > /dev/null 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $out -- python3 $root/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-micro "$@" > /dev/null 2>&1
 python3 - "$out" "$max" <<'PY'
 import csv, glob, sys, re, collections
 rows = []

@@ -603,7 +603,7 @@ root = os.environ["ZIRA_ROOT"]
 cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
        "--master-port", os.environ["ZIRA_PORT"], os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
        "--no-cpu-baseline", "--no-second-mode", "--kernel-timing-steps", "1", "--height", "320", "--width", "448",
-       "--force-collectives"]
+       "--force-collectives", "--full"]
 p = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
 lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
 assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
@@ -634,7 +634,7 @@ import json, os, subprocess, sys
 root = os.environ["ZIRA_ROOT"]
 cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
        "--master-port", os.environ["ZIRA_PORT"], os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-       "--no-second-mode", "--kernel-timing-steps", "1", "--height", "256", "--width", "320"]
+       "--no-second-mode", "--kernel-timing-steps", "1", "--height", "256", "--width", "320", "--full"]
 env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", ZIRA_BENCH_DEVICE="0", ZIRA_BENCH_BACKEND="gloo")
 p = subprocess.run(cmd, capture_output=True, text=True, timeout=1700, env=env)
 lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -647,7 +647,7 @@ print("BENCH-TWO-RANKS-OK %.2f images/s" % line["value"])
 
 
 def test_bench_control_flow_with_two_ranks_on_one_gpu():
-    """The whole default `bench.py` path at N = 2 -- two ranks under `torch.distributed.run`, both pinned to the box's one
+    """The whole `bench.py --full` path at N = 2 -- two ranks under `torch.distributed.run`, both pinned to the box's one
     GPU, collectives over gloo (RCCL refuses two ranks on a device): warm-up, the timed region between its barriers, the
     eager MSDA timing steps, the in-model capture step (collective: every rank), rank 0's micro-benchmarks while rank 1
     waits in the MAX all-reduce of the timings, one JSON line with the aggregate.  Round 4 found rank 0 running the capture

@@ -693,3 +693,29 @@ def test_shares_of_split_tiles_combine_inside_the_launch_under_load(oracle, name
         err = float((gv - t(want[it & 1])).abs().max()) / scale[it & 1]
         assert err < 2e-5, (name, it, err)
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("name,kw", [("inmodel", dict(inmodel=True)), ("pinpoint", dict(hot=2)), ("hot", dict(hot=True))])
+def test_planned_backward_is_run_to_run_identical_with_split_tiles(name, kw):
+    """Which records a share of a split tile holds follows the plan's atomic ranks, so it changes from plan to plan; the
+    shares' sums stay in double until the fixed-order fold rounds them once, so grad_value (and the rest) come out the same.
+    (Rounded to fp32 per share, ~0.4 % of grad_value differed between two plans of the same call at the model's shape -- and a
+    training run amplifies a last-bit difference in one step into percent-level differences a few steps later.)  The double
+    sums still depend on the order of the LDS adds; an fp32 result that differs needs a last-bit difference of a double on an
+    fp32 rounding boundary -- pinpoint, with thousands of adds on each of a few hundred words, is the likeliest case for it."""
+    from ziragroundingdino_amd import _C
+
+    B, Q, M, D, shapes, P = 2, 900, 8, 32, NORTH_STAR_SHAPES, 4
+    value, sh, start, loc, attn, go = _random_case(B, Q, M, D, shapes, P, seed=57, **kw)
+    t = lambda a: torch.from_numpy(a).to(DEV)
+    args = list(map(t, (value, sh, start, loc, attn)))
+    tgo = t(go)
+    first = None
+    for _ in range(4):
+        out, plan = _C.ms_deform_attn_forward_plan(*args, 64)   # a fresh plan each time: fresh ranks inside the tiles
+        got = [out] + list(_C.ms_deform_attn_backward(*args, tgo, 64, plan=plan))
+        if first is None:
+            first = got
+            continue
+        for what, a, b in zip(("output", "grad_value", "grad_loc", "grad_attn"), first, got):
+            assert torch.equal(a, b), (name, what, int((a != b).sum()))

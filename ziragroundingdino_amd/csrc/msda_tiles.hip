@@ -142,7 +142,7 @@ struct PlanPtrs {
     unsigned *ucnt;     // [units][kUcnt] items of a unit per size class, and the unit's first item slot
     unsigned *tcnt;     // [units * ecap]       shares of a split tile that have stored their partial tile (indexed by the tile's first
                         //                      partial tile; zero between launches: the plan clears them, the last arriver resets its own)
-    float *partial;     // [units * ecap][kNPix * 32]  sums of the shares of split tiles (written by the accumulate kernel)
+    double *partial;    // [units * ecap][kNPix * 32]  sums of the shares of split tiles, in double (written by the accumulate kernel)
     uint4 *citems;      // [kClasses][ccap][2]  items by size class, a unit's at its own slots
     uint4 *recs;        // [units * rcap]       16-byte records, sorted by tile inside a unit
 };
@@ -557,7 +557,7 @@ struct HomeArgs {
 template <unsigned NTHR>
 __global__ __launch_bounds__(NTHR, ZIRA_TILE_SLOTS_PER_CU) void msda_bwd_tile_accum(
     const float *__restrict__ grad_out, PlanGeom G, const unsigned *__restrict__ ucnt, const uint4 *__restrict__ citems,
-    const uint4 *__restrict__ recs, float *__restrict__ dump, float *partial, unsigned *tcnt, float *__restrict__ grad_value,
+    const uint4 *__restrict__ recs, float *__restrict__ dump, double *partial, unsigned *tcnt, float *__restrict__ grad_value,
     const HomeArgs HA)
 {
     BTIME_DECL;
@@ -809,15 +809,24 @@ __global__ __launch_bounds__(NTHR, ZIRA_TILE_SLOTS_PER_CU) void msda_bwd_tile_ac
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "msda_bwd_tile_accum's in-launch hand-off is validated for gfx950 only (write-through stores + sc1 loads)"
 #endif
+                // The partial tiles hold the shares' sums in DOUBLE, and the fold rounds to fp32 once.  Which records a share
+                // holds follows the plan's atomic ranks and changes from run to run; with each share rounded to fp32 first,
+                // ~0.4 % of grad_value differed between two identical calls at the model's decoder shape.  The double sums
+                // still depend on the order of the LDS adds (products of fp32 factors are exact in double, sums of terms of
+                // different exponents are not), so an fp32 result can still differ, but only where a difference in the last
+                // bits of a double lands on an fp32 rounding boundary: rare, not impossible.
                 typedef unsigned long long u64;
-                const size_t toff = (size_t)p0 * D + c4 * 4;          // this thread's float4 of a tile, round 0
+                const size_t toff = (size_t)p0 * D + c4 * 4;          // this thread's four channels of a tile, round 0
                 u64 *pb = reinterpret_cast<u64 *>(partial + (size_t)it.slot * kNPix * D + toff);
 #pragma unroll
                 for (unsigned ii = 0; ii < NR; ++ii) {
-                    const float4 o = take4(ii);
-                    u64 *q = pb + (size_t)ii * PPR * D / 2;
-                    __hip_atomic_store(q, ((u64)__float_as_uint(o.y) << 32) | __float_as_uint(o.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(q + 1, ((u64)__float_as_uint(o.w) << 32) | __float_as_uint(o.z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    double *w = reinterpret_cast<double *>(lp + ii * kRound);   // (take4's words, read and cleared unrounded)
+                    u64 *q = pb + (size_t)ii * PPR * D;
+#pragma unroll
+                    for (unsigned j = 0; j < 4; ++j) {
+                        __hip_atomic_store(q + j, (u64)__double_as_longlong(w[8 * j]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        w[8 * j] = 0.0;
+                    }
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave: its partial tile has left
                 __syncthreads();
@@ -828,18 +837,17 @@ __global__ __launch_bounds__(NTHR, ZIRA_TILE_SLOTS_PER_CU) void msda_bwd_tile_ac
                     const u64 *p0k = reinterpret_cast<const u64 *>(partial + (size_t)(it.slot - it.kshare) * kNPix * D + toff);
 #pragma unroll
                     for (unsigned ii = 0; ii < NR; ++ii) {
-                        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+                        double a[4] = {0.0, 0.0, 0.0, 0.0};
                         for (unsigned kk = 0; kk < it.nshare; ++kk) {   // (fixed order: the same sum in every run)
-                            const u64 *q = p0k + (size_t)kk * kNPix * D / 2 + (size_t)ii * PPR * D / 2;
-                            const u64 lo = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const u64 hi = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const float4 b = make_float4(__uint_as_float((unsigned)lo), __uint_as_float((unsigned)(lo >> 32)),
-                                                         __uint_as_float((unsigned)hi), __uint_as_float((unsigned)(hi >> 32)));
-                            if (kk == 0) a = b;
-                            else { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+                            const u64 *q = p0k + (size_t)kk * kNPix * D + (size_t)ii * PPR * D;
+#pragma unroll
+                            for (unsigned j = 0; j < 4; ++j) {
+                                const double b = __longlong_as_double((long long)__hip_atomic_load(q + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                                a[j] = kk == 0 ? b : a[j] + b;
+                            }
                         }
                         float *dst = (colin && (PPR / kTW) * ii + pr0 < it.the) ? gbase + ii * rstep : dump + 192 + 4 * lane;
-                        *reinterpret_cast<float4 *>(dst) = a;
+                        *reinterpret_cast<float4 *>(dst) = make_float4((float)a[0], (float)a[1], (float)a[2], (float)a[3]);
                     }
                     if (tid == 0) __hip_atomic_store(tc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the plan may serve another backward)
                 }
@@ -927,7 +935,7 @@ inline bool make_tiles_layout(int B, int S, int M, int D, int L, int Q, int P, T
     T.off_dump = o;   o += 2048;                                            // where redirected stores go (never read)
     T.off_recs = o;   o += align256((size_t)T.units * G.rcap * 16) + 256;   // (+ pad: record 0 of an empty tail item)
     if ((unsigned long long)T.units * G.ecap >= (1ull << 24)) return false;   // 24-bit partial-tile index
-    T.off_partial = o; o += align256((size_t)T.units * G.ecap * kNPix * 32 * 4);   // (worst case; what is touched is one 16 KB tile per share)
+    T.off_partial = o; o += align256((size_t)T.units * G.ecap * kNPix * 32 * 8);   // (worst case, in double; what is touched is one 32 KB tile per share)
     T.total = o;
     return true;
 }
@@ -952,7 +960,7 @@ inline PlanPtrs plan_ptrs(const TilesLayout &T, void *plan)
     PlanPtrs W;
     W.ucnt = reinterpret_cast<unsigned *>(w);
     W.tcnt = reinterpret_cast<unsigned *>(w + T.off_tcnt);
-    W.partial = reinterpret_cast<float *>(w + T.off_partial);
+    W.partial = reinterpret_cast<double *>(w + T.off_partial);
     W.citems = reinterpret_cast<uint4 *>(w + T.off_citems);
     W.recs = reinterpret_cast<uint4 *>(w + T.off_recs);
     return W;
