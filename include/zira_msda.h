@@ -444,6 +444,16 @@ int zira_split_f16x2_frag_f32(const float *w, int rows, int cols, int transpose,
 int zira_gemm_f16x2_panel_f32(const float *A, const float *A2, const void *b_frags, int M, int N, int K, int epilogue,
                               const float *bias, const float *aux, float *C, void *stream);
 
+/* ---- The same products for a padded minibatch: row_mask [M] bytes, row_mask[m] != 0 marks row m as padding, whose product
+ * is treated as absent (reference ms_deform_attn.py:287-288: value.masked_fill(key_padding_mask, 0) after the projection):
+ *   0: C's row is exact zeros (not the bias);
+ *   3: C's row equals aux's row (the input gradient through that masked_fill: the incoming gradient's padded rows are
+ *      zero); in place (C == aux) nothing of it is stored.
+ * A select, not a multiply: NaN or Inf in a padded row of A does not reach C.  Blocks of 32 padded rows skip their loads.
+ * Any other epilogue with a mask: -1.  row_mask NULL: exactly zira_gemm_f16x2_panel_f32. */
+int zira_gemm_f16x2_panel_masked_f32(const float *A, const float *A2, const void *b_frags, int M, int N, int K, int epilogue,
+                                     const float *bias, const float *aux, const unsigned char *row_mask, float *C, void *stream);
+
 /* ---- The frozen feed-forward block as ONE launch per direction, on the f16 matrix cores in fp32 accuracy ----
  * forward   y  = relu(x W1^T + b1) W2^T + b2        (reference FFN: transformer_for_adapter.py:877-886)
  * backward  gx = aux + ((gy W2) * [h > 0]) W1       (its autograd under the freeze of

@@ -24,6 +24,7 @@ SYMBOLS = (
     "zira_sine_embed_f32", "zira_attn_fwd_f32", "zira_attn_bwd_f32", "zira_attn_bwd_ld_f32", "zira_attn_bwd_scratch_floats", "zira_msda_sampling_fwd_f32", "zira_msda_sampling_bwd_f32", "zira_gemm_drelu_f32",
     "zira_rowgemm_f32", "zira_box_refine_fwd_f32", "zira_box_refine_bwd_f32", "zira_decoder_prep_f32",
     "zira_split_bf16x3_f32", "zira_gemm_bf16x3_f32", "zira_split_f16x2_f32", "zira_gemm_f16x2_f32", "zira_gemm_f16x2_ex_f32", "zira_split_f16x2_frag_f32", "zira_gemm_f16x2_panel_f32",
+    "zira_gemm_f16x2_panel_masked_f32",
     "zira_ffn_f16x2_pack_bytes", "zira_ffn_f16x2_workspace_bytes", "zira_ffn_f16x2_pack_f32", "zira_ffn_f16x2_f32",
     "zira_thin_f16x2_frag_bytes", "zira_thin_f16x2_split_f32", "zira_thin_f16x2_f32",
     "zira_xty_bf16x3_workspace_floats", "zira_xty_bf16x3_f32",
@@ -199,6 +200,8 @@ def load():
     lib.zira_split_f16x2_frag_f32.restype = i
     lib.zira_gemm_f16x2_panel_f32.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp]
     lib.zira_gemm_f16x2_panel_f32.restype = i
+    lib.zira_gemm_f16x2_panel_masked_f32.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp, vp]
+    lib.zira_gemm_f16x2_panel_masked_f32.restype = i
     lib.zira_ffn_f16x2_pack_bytes.argtypes = [i]
     lib.zira_ffn_f16x2_pack_bytes.restype = ctypes.c_size_t
     lib.zira_ffn_f16x2_pack_f32.argtypes = [vp, ll, ll, vp, ll, ll, vp, i, vp, vp]

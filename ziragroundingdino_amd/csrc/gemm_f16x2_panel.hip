@@ -48,17 +48,39 @@ __device__ __forceinline__ void pow2_scale(float amax, float &s, float &inv)
 }
 
 // KS = K / 16 matrix-core steps.  LDS: planes [2][KS][2 halves of a step][32 rows][8 halves] = 2 KS KB, then 32 floats (1 / scale).
-template <int KS, int EPI, bool ADD2>
+// MASKED (EPI_BIAS / EPI_ADD only): row_mask[m] != 0 marks row m as padding, whose product is absent -- EPI_BIAS writes zeros
+// (masked_fill after the projection), EPI_ADD writes aux (the input gradient through that masked_fill).  A select, not a
+// multiply: whatever a padded row of A holds (NaN, Inf) stays in its own accumulator row and is dropped.
+template <int KS, int EPI, bool ADD2, bool MASKED>
 __global__ __launch_bounds__(kThreads, 4) void gemm_f16x2_panel_kernel(const float *__restrict__ A, const float *__restrict__ A2,
                                                                     const unsigned char *__restrict__ Wf, const float *__restrict__ winv,
-                                                                    const float *__restrict__ bias, const float *aux, float *C, int M,
-                                                                    int N)
+                                                                    const float *__restrict__ bias, const float *aux,
+                                                                    const unsigned char *__restrict__ row_mask, float *C, int M, int N)
 {
     constexpr int K = 16 * KS, J = K / 32;                 // J float4 per thread: thread (row, c) takes columns 4 c + 32 j
     __shared__ __attribute__((aligned(16))) unsigned char planes[2 * KS * 1024];
     __shared__ float sinv[kRows];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int m0 = blockIdx.x * kRows;
+
+    if (MASKED) {
+        // every wave reads the block's 32 mask bytes and reaches the same verdict, so the exit below is block-uniform and comes
+        // before the only barrier (rows past the end count as padding: nothing of theirs is stored)
+        const int mr = m0 + (lane & 31);
+        const bool all_padding = __all(mr >= M || row_mask[mr] != 0);
+        if (all_padding) {
+            if (EPI == EPI_ADD && C == aux) return;
+            const int row = tid >> 3, c = tid & 7, m = m0 + row;
+            if (m < M) {
+                for (int n = 4 * c; n < N; n += 32) {
+                    const size_t at = (size_t)m * N + n;
+                    const float4 o = EPI == EPI_ADD ? *reinterpret_cast<const float4 *>(aux + at) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    *reinterpret_cast<float4 *>(C + at) = o;
+                }
+            }
+            return;
+        }
+    }
 
     // ---- the panel: all of it requested at once ---------------------------------------------------------------------------------
     {
@@ -106,6 +128,7 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x2_panel_kernel(const flo
     const int lm = lane & 31, hf = lane >> 5;
     const int m = m0 + lm;
     const float inv = sinv[lm];
+    const bool padded = MASKED && m < M && row_mask[m] != 0;
     const unsigned char *pa = planes + hf * 512 + lm * 16;
     const int ntiles = N >> 5;
     for (int t = wave; t < ntiles; t += 4) {
@@ -153,6 +176,9 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x2_panel_kernel(const flo
                     if (EPI == EPI_BIAS_RELU) {
                         o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
                     }
+                    if (MASKED) {
+                        o.x = padded ? 0.f : o.x; o.y = padded ? 0.f : o.y; o.z = padded ? 0.f : o.z; o.w = padded ? 0.f : o.w;
+                    }
                 } else {
                     const float4 h = *reinterpret_cast<const float4 *>(aux + at);
                     if (EPI == EPI_MASK) {
@@ -160,6 +186,9 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x2_panel_kernel(const flo
                         o.z = h.z > 0.f ? o.z : 0.f; o.w = h.w > 0.f ? o.w : 0.f;
                     } else {
                         o.x += h.x; o.y += h.y; o.z += h.z; o.w += h.w;
+                        if (MASKED) {
+                            o.x = padded ? h.x : o.x; o.y = padded ? h.y : o.y; o.z = padded ? h.z : o.z; o.w = padded ? h.w : o.w;
+                        }
                     }
                 }
                 *reinterpret_cast<float4 *>(C + at) = o;
@@ -202,14 +231,22 @@ __global__ __launch_bounds__(256) void split_f16x2_frag_kernel(const float *__re
 
 template <int KS, bool ADD2>
 int launch_epi(int epi, const float *a, const float *a2, const unsigned char *wf, const float *winv, const float *bias, const float *aux,
-               float *c, int M, int N, hipStream_t st)
+               const unsigned char *row_mask, float *c, int M, int N, hipStream_t st)
 {
     const dim3 grid((M + kRows - 1) / kRows), block(kThreads);
+    if (row_mask) {
+        switch (epi) {
+        case EPI_BIAS: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_BIAS, ADD2, true>), grid, block, 0, st, a, a2, wf, winv, bias, aux, row_mask, c, M, N); break;
+        case EPI_ADD: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_ADD, ADD2, true>), grid, block, 0, st, a, a2, wf, winv, bias, aux, row_mask, c, M, N); break;
+        default: return -1;
+        }
+        return (int)hipGetLastError();
+    }
     switch (epi) {
-    case EPI_BIAS: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_BIAS, ADD2>), grid, block, 0, st, a, a2, wf, winv, bias, aux, c, M, N); break;
-    case EPI_BIAS_RELU: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_BIAS_RELU, ADD2>), grid, block, 0, st, a, a2, wf, winv, bias, aux, c, M, N); break;
-    case EPI_MASK: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_MASK, ADD2>), grid, block, 0, st, a, a2, wf, winv, bias, aux, c, M, N); break;
-    case EPI_ADD: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_ADD, ADD2>), grid, block, 0, st, a, a2, wf, winv, bias, aux, c, M, N); break;
+    case EPI_BIAS: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_BIAS, ADD2, false>), grid, block, 0, st, a, a2, wf, winv, bias, aux, nullptr, c, M, N); break;
+    case EPI_BIAS_RELU: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_BIAS_RELU, ADD2, false>), grid, block, 0, st, a, a2, wf, winv, bias, aux, nullptr, c, M, N); break;
+    case EPI_MASK: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_MASK, ADD2, false>), grid, block, 0, st, a, a2, wf, winv, bias, aux, nullptr, c, M, N); break;
+    case EPI_ADD: hipLaunchKernelGGL((gemm_f16x2_panel_kernel<KS, EPI_ADD, ADD2, false>), grid, block, 0, st, a, a2, wf, winv, bias, aux, nullptr, c, M, N); break;
     default: return -1;
     }
     return (int)hipGetLastError();
@@ -230,18 +267,33 @@ extern "C" int zira_split_f16x2_frag_f32(const float *w, int rows, int cols, int
     return (int)hipGetLastError();
 }
 
-extern "C" int zira_gemm_f16x2_panel_f32(const float *a, const float *a2, const void *b_frags, int M, int N, int K, int epilogue,
-                                         const float *bias, const float *aux, float *c, void *stream_)
+static int panel_launch(const float *a, const float *a2, const void *b_frags, int M, int N, int K, int epilogue, const float *bias,
+                        const float *aux, const unsigned char *row_mask, float *c, void *stream_)
 {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!a || !b_frags || !c || M <= 0 || N <= 0 || N % 32 || (K != 256 && K != 384)) return -1;
     if ((epilogue == EPI_BIAS || epilogue == EPI_BIAS_RELU) ? !bias : !aux) return -1;
+    if (row_mask && epilogue != EPI_BIAS && epilogue != EPI_ADD) return -1;
     if (((uintptr_t)a | (uintptr_t)a2 | (uintptr_t)b_frags | (uintptr_t)c | (uintptr_t)bias | (uintptr_t)aux) & 15) return -1;
     const unsigned char *wf = reinterpret_cast<const unsigned char *>(b_frags);
     const float *winv = reinterpret_cast<const float *>(wf + (size_t)4 * N * K);
     if (K == 256)
-        return a2 ? launch_epi<16, true>(epilogue, a, a2, wf, winv, bias, aux, c, M, N, stream)
-                  : launch_epi<16, false>(epilogue, a, a2, wf, winv, bias, aux, c, M, N, stream);
-    return a2 ? launch_epi<24, true>(epilogue, a, a2, wf, winv, bias, aux, c, M, N, stream)
-              : launch_epi<24, false>(epilogue, a, a2, wf, winv, bias, aux, c, M, N, stream);
+        return a2 ? launch_epi<16, true>(epilogue, a, a2, wf, winv, bias, aux, row_mask, c, M, N, stream)
+                  : launch_epi<16, false>(epilogue, a, a2, wf, winv, bias, aux, row_mask, c, M, N, stream);
+    return a2 ? launch_epi<24, true>(epilogue, a, a2, wf, winv, bias, aux, row_mask, c, M, N, stream)
+              : launch_epi<24, false>(epilogue, a, a2, wf, winv, bias, aux, row_mask, c, M, N, stream);
+}
+
+extern "C" int zira_gemm_f16x2_panel_f32(const float *a, const float *a2, const void *b_frags, int M, int N, int K, int epilogue,
+                                         const float *bias, const float *aux, float *c, void *stream_)
+{
+    return panel_launch(a, a2, b_frags, M, N, K, epilogue, bias, aux, nullptr, c, stream_);
+}
+
+// row_mask [M] bytes, nonzero = padding row (EPI_BIAS: zeros, EPI_ADD: aux; other epilogues -1); null = zira_gemm_f16x2_panel_f32
+extern "C" int zira_gemm_f16x2_panel_masked_f32(const float *a, const float *a2, const void *b_frags, int M, int N, int K, int epilogue,
+                                                const float *bias, const float *aux, const unsigned char *row_mask, float *c,
+                                                void *stream_)
+{
+    return panel_launch(a, a2, b_frags, M, N, K, epilogue, bias, aux, row_mask, c, stream_);
 }

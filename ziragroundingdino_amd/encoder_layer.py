@@ -11,7 +11,11 @@ here the residual path joins as well: the LayerNorm input gradient ``gs`` is the
     gsrc = gs + gv Wv + gproj Wq            (addmm_ into gs, twice)
 
 The forward is the module's own sequence of launches (two projections, sampling locations + softmax, the MSDA op, output
-projection, residual add + LayerNorm in one kernel).  fp32 GPU calls without padding mask only; otherwise the modules run."""
+projection, residual add + LayerNorm in one kernel).  fp32 GPU calls without padding mask (``applies``), or with a [B, S]
+padding mask on the same device (``padded_applies``); otherwise the modules run.  With a mask, as in the reference
+(ms_deform_attn.py:287-288), only the value is masked: its padded rows are zeros, so the value projection writes zeros there
+and the gradient of those rows does not reach ``src`` through it -- both inside the panel kernel under ``f16x2``
+(zira_gemm_f16x2_panel_masked_f32), a ``masked_fill_`` otherwise."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -20,9 +24,22 @@ from . import gemm_bf16x3 as g3
 
 
 def applies(layer, src, pos, reference_points, spatial_shapes, key_padding_mask) -> bool:
+    return key_padding_mask is None and _node_ok(layer, src, pos, reference_points, spatial_shapes)
+
+
+def padded_applies(layer, src, pos, reference_points, spatial_shapes, key_padding_mask) -> bool:
+    """As ``applies`` for a call WITH a padding mask: a [B, S] bool mask on ``src``'s device."""
+    if not (isinstance(key_padding_mask, torch.Tensor) and key_padding_mask.dtype == torch.bool and key_padding_mask.is_cuda):
+        return False
+    if key_padding_mask.device != src.device or src.dim() != 3 or tuple(key_padding_mask.shape) != tuple(src.shape[:2]):
+        return False
+    return _node_ok(layer, src, pos, reference_points, spatial_shapes)
+
+
+def _node_ok(layer, src, pos, reference_points, spatial_shapes) -> bool:
     from .ms_deform_attn import _frozen_fp32_linear, _sampling_plan_ok
     ms, norm = layer.self_attn, layer.norm1
-    if key_padding_mask is not None or pos is None or not src.is_cuda or src.dtype != torch.float32 or src.dim() != 3:
+    if pos is None or not src.is_cuda or src.dtype != torch.float32 or src.dim() != 3:
         return False
     if torch.is_autocast_enabled("cuda") or pos.requires_grad or (layer.training and layer.dropout1.p > 0.0):
         return False
@@ -48,7 +65,7 @@ def applies(layer, src, pos, reference_points, spatial_shapes, key_padding_mask)
 
 class _FrozenEncoderAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, layer, src, pos, ref, shapes, level_start):
+    def forward(ctx, layer, src, pos, ref, shapes, level_start, key_padding_mask=None):
         lib = _lib.load()
         ms, norm = layer.self_attn, layer.norm1
         wq, bq = ms._fused_query_projection()
@@ -62,16 +79,20 @@ class _FrozenEncoderAttention(torch.autograd.Function):
         rows = B * S
         f32 = dict(dtype=torch.float32, device=dev)
         s2 = src.view(rows, C)
+        rm = None if key_padding_mask is None else key_padding_mask.reshape(rows)   # [B S] rows, True = padding
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             arith = g3.enabled() and g3.supported(s2, C, C) and g3.supported(s2, wq.shape[0], C)
             if arith:   # the 256-wide products on the matrix cores in split arithmetic (gemm_bf16x3.py); the position code is
                 #         added to the query inside the kernel where the panel kernel takes the product
-                value = g3.linear(ms, "value", s2, wv, bv).view(B, S, M, C // M)
+                value = g3.linear(ms, "value", s2, wv, bv, row_mask=rm).view(B, S, M, C // M)
                 proj = g3.linear(ms, "query", s2, wq, bq, add=pos.contiguous().view(rows, C))
             else:
                 sp = (src + pos).view(rows, C)
-                value = torch.addmm(bv, s2, wv.t()).view(B, S, M, C // M)
+                value = torch.addmm(bv, s2, wv.t())
+                if rm is not None:
+                    value.masked_fill_(rm[:, None], 0.0)
+                value = value.view(B, S, M, C // M)
                 proj = torch.addmm(bq, sp, wq.t())
             nproj = proj.shape[1]
             loc = torch.empty((B, S, M, L, P, 2), **f32)
@@ -92,13 +113,13 @@ class _FrozenEncoderAttention(torch.autograd.Function):
         ctx.layer = layer
         ctx.dims = (B, S, C, M, L, P, R, nproj)
         ctx.arith = arith
-        ctx.save_for_backward(value, loc, attn, ref, s, stats, shapes, level_start, wq)
+        ctx.save_for_backward(value, loc, attn, ref, s, stats, shapes, level_start, wq, rm)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        value, loc, attn, ref, s, stats, shapes, level_start, wq = ctx.saved_tensors
+        value, loc, attn, ref, s, stats, shapes, level_start, wq, rm = ctx.saved_tensors
         lib = _lib.load()
         ms, norm = ctx.layer.self_attn, ctx.layer.norm1
         B, S, C, M, L, P, R, nproj = ctx.dims
@@ -125,17 +146,22 @@ class _FrozenEncoderAttention(torch.autograd.Function):
                 raise RuntimeError("zira_msda_sampling_bwd_f32 failed with code %d" % rc)
             # the three gradients of src meet in the GEMMs: residual path as the addend, then the two projections
             # (in place: torch.addmm(x, ...) would first COPY x into its result -- a pass of its own; gs is this node's)
+            # (padding: the value's padded rows were zeroed after its projection, so gv's padded rows do not flow back)
             if ctx.arith:
-                gx = g3.linear_input_grad(ms, "value", gv.view(rows, C), ms.value_proj.weight, accumulate_into=gs2)
+                gx = g3.linear_input_grad(ms, "value", gv.view(rows, C), ms.value_proj.weight, accumulate_into=gs2, row_mask=rm)
                 g3.linear_input_grad(ms, "query", gproj, wq, accumulate_into=gx)
             else:
-                gx = gs2.addmm_(gv.view(rows, C), ms.value_proj.weight)
+                gv2 = gv.view(rows, C)
+                if rm is not None:
+                    gv2.masked_fill_(rm[:, None], 0.0)
+                gx = gs2.addmm_(gv2, ms.value_proj.weight)
                 gx.addmm_(gproj, wq)
-        return None, gx.view(B, S, C), None, None, None, None
+        return None, gx.view(B, S, C), None, None, None, None, None
 
 
-def attention_sublayer(layer, src, pos, reference_points, spatial_shapes, level_start_index):
-    """norm1(src + self_attn(src + pos, reference_points, src)) of a frozen encoder layer; call only when ``applies()``."""
+def attention_sublayer(layer, src, pos, reference_points, spatial_shapes, level_start_index, key_padding_mask=None):
+    """norm1(src + self_attn(src + pos, reference_points, src, key_padding_mask)) of a frozen encoder layer; call only when
+    ``applies()`` (no mask) or ``padded_applies()`` (a [B, S] mask, True = padding)."""
     from .ms_deform_attn import _check_levels_cover_value
     _check_levels_cover_value(spatial_shapes, src.shape[1], level_start_index)
-    return _FrozenEncoderAttention.apply(layer, src, pos, reference_points, spatial_shapes, level_start_index)
+    return _FrozenEncoderAttention.apply(layer, src, pos, reference_points, spatial_shapes, level_start_index, key_padding_mask)

@@ -168,9 +168,18 @@ def gemm_f16x2(a: torch.Tensor, planes: torch.Tensor, N: int, epilogue: int, bia
     return out
 
 
+def _row_mask_bytes(row_mask: torch.Tensor, M: int, device) -> torch.Tensor:
+    """``row_mask`` [M] bool / uint8 on ``device`` -> its bytes as a contiguous uint8 tensor (nonzero = padding row)."""
+    assert row_mask.device == device and row_mask.dtype in (torch.bool, torch.uint8) and row_mask.numel() == M
+    rm = row_mask.reshape(M).contiguous()
+    return rm.view(torch.uint8) if rm.dtype == torch.bool else rm
+
+
 def gemm_f16x2_panel(a: torch.Tensor, frags: torch.Tensor, N: int, epilogue: int, bias: torch.Tensor = None, aux: torch.Tensor = None,
-                     out: torch.Tensor = None, add: torch.Tensor = None) -> torch.Tensor:
-    """epilogue((a [+ add]) [M, K] @ B^T) -> [M, N] with B = ``frags`` (split_frags_f16x2 of an [N, K] weight), K = 256 or 384."""
+                     out: torch.Tensor = None, add: torch.Tensor = None, row_mask: torch.Tensor = None) -> torch.Tensor:
+    """epilogue((a [+ add]) [M, K] @ B^T) -> [M, N] with B = ``frags`` (split_frags_f16x2 of an [N, K] weight), K = 256 or 384.
+    ``row_mask`` [M] (bool / uint8, nonzero = padding; EPI_BIAS / EPI_ADD only): the product of those rows is absent --
+    EPI_BIAS writes zeros there, EPI_ADD leaves ``aux``'s row (zira_gemm_f16x2_panel_masked_f32)."""
     M, K = a.shape
     assert panel_supported(N, K) and frags.shape == (2 * N * K + 2 * N,) and frags.dtype == torch.int16 and frags.device == a.device
     if out is None:
@@ -182,6 +191,15 @@ def gemm_f16x2_panel(a: torch.Tensor, frags: torch.Tensor, N: int, epilogue: int
         assert aux.shape == (M, N) and aux.is_contiguous() and aux.dtype == torch.float32
     if add is not None:
         assert add.shape == a.shape and add.is_contiguous() and add.dtype == torch.float32 and add.data_ptr() % 16 == 0
+    if row_mask is not None:
+        rm = _row_mask_bytes(row_mask, M, a.device)
+        with torch.cuda.device(a.device):
+            rc = _lib.load().zira_gemm_f16x2_panel_masked_f32(a.data_ptr(), 0 if add is None else add.data_ptr(), frags.data_ptr(), M, N, K,
+                                                              epilogue, 0 if bias is None else bias.data_ptr(),
+                                                              0 if aux is None else aux.data_ptr(), rm.data_ptr(), out.data_ptr(), _stream(a))
+        if rc != 0:
+            raise RuntimeError("zira_gemm_f16x2_panel_masked_f32 failed with code %d (M=%d N=%d K=%d epilogue=%d)" % (rc, M, N, K, epilogue))
+        return out
     with torch.cuda.device(a.device):
         rc = _lib.load().zira_gemm_f16x2_panel_f32(a.data_ptr(), 0 if add is None else add.data_ptr(), frags.data_ptr(), M, N, K, epilogue,
                                                    0 if bias is None else bias.data_ptr(), 0 if aux is None else aux.data_ptr(),
@@ -217,24 +235,32 @@ def _cache(owner, name, transpose, N, K):
     return sw
 
 
-def _gemm_cached(sw, a, weight, N, epilogue, add=None, **kw):
+def _gemm_cached(sw, a, weight, N, epilogue, add=None, row_mask=None, **kw):
     planes = sw.planes(weight)
     if sw.panel:
-        return gemm_f16x2_panel(a, planes, N, epilogue, add=add, **kw)
+        return gemm_f16x2_panel(a, planes, N, epilogue, add=add, row_mask=row_mask, **kw)
     if add is not None:
         a = a + add
+    if row_mask is not None and epilogue == EPI_ADD:    # (a zero row adds nothing: the padded rows keep aux exactly)
+        a = a.masked_fill(row_mask.reshape(-1, 1).bool(), 0.0)
     if sw.f16x2:
-        return gemm_f16x2(a, planes, N, epilogue, **kw)
-    return gemm(a, planes, epilogue, **kw)
+        out = gemm_f16x2(a, planes, N, epilogue, **kw)
+    else:
+        out = gemm(a, planes, epilogue, **kw)
+    if row_mask is not None and epilogue == EPI_BIAS:
+        out.masked_fill_(row_mask.reshape(-1, 1).bool(), 0.0)
+    return out
 
 
-def linear(owner, name, x2, weight, bias=None, out=None, add=None):
+def linear(owner, name, x2, weight, bias=None, out=None, add=None, row_mask=None):
     """``(x2 [+ add]) @ weight.T (+ bias)`` for a frozen ``weight`` [N, K]; the planes are cached on ``owner`` under ``name``.
-    ``add`` [M, K]: a second operand summed with ``x2`` on the way in (inside the panel kernel where it takes the product)."""
+    ``add`` [M, K]: a second operand summed with ``x2`` on the way in (inside the panel kernel where it takes the product).
+    ``row_mask`` [M] bool / uint8 on the GPU: rows marked nonzero come out as zeros (``masked_fill`` after the projection,
+    reference ms_deform_attn.py:287-288) -- inside the panel kernel, else one ``masked_fill_``."""
     N, K = weight.shape
     if bias is None:
         bias = _zeros(N, x2.device)
-    return _gemm_cached(_cache(owner, name, False, N, K), x2, weight, N, EPI_BIAS, add=add, bias=bias, out=out)
+    return _gemm_cached(_cache(owner, name, False, N, K), x2, weight, N, EPI_BIAS, add=add, bias=bias, out=out, row_mask=row_mask)
 
 
 def linear_tiled_f16x2(owner, name, x2, weight, bias, epilogue=EPI_BIAS, residual=None, row_scale=None, rows_per_scale=0, out=None):
@@ -251,14 +277,16 @@ def linear_tiled_f16x2(owner, name, x2, weight, bias, epilogue=EPI_BIAS, residua
                       rows_per_scale=rows_per_scale)
 
 
-def linear_input_grad(owner, name, g2, weight, accumulate_into=None):
+def linear_input_grad(owner, name, g2, weight, accumulate_into=None, row_mask=None):
     """``g2 @ weight`` for a frozen ``weight`` [N_out, K_in] (the input gradient of ``F.linear``): [M, N_out] -> [M, K_in];
-    ``accumulate_into`` [M, K_in]: added to IN PLACE (the gradient that meets this one) and returned."""
+    ``accumulate_into`` [M, K_in]: added to IN PLACE (the gradient that meets this one) and returned.
+    ``row_mask`` [M]: the rows of ``g2`` marked nonzero count as zero (the gradient through a ``masked_fill`` of the output):
+    those rows of the result are zeros, or keep ``accumulate_into``'s values."""
     K, N = weight.shape                                             # B[n][k] = weight[k][n]
     sw = _cache(owner, name, True, N, K)
     if accumulate_into is not None:
-        return _gemm_cached(sw, g2, weight, N, EPI_ADD, aux=accumulate_into, out=accumulate_into)
-    return _gemm_cached(sw, g2, weight, N, EPI_BIAS, bias=_zeros(N, g2.device))
+        return _gemm_cached(sw, g2, weight, N, EPI_ADD, aux=accumulate_into, out=accumulate_into, row_mask=row_mask)
+    return _gemm_cached(sw, g2, weight, N, EPI_BIAS, bias=_zeros(N, g2.device), row_mask=row_mask)
 
 
 _ZEROS = {}

@@ -147,27 +147,34 @@ class _MultiValueProjections(Function):
     """The value projections of SEVERAL deformable-attention modules on one source (the six decoder layers all read the
     encoder's output, reference transformer_for_adapter.py:1059 inside the loop :700-806) as one autograd node, frozen
     weights: the input gradient is one buffer that the n products accumulate into, instead of n tensors of 45 MB and n - 1
-    adds.  ``wb`` = n weights, then n biases."""
+    adds.  ``wb`` = n weights, then n biases.  ``mask`` (or None): the [B, S] padding mask of ``x`` [B, S, C], applied to every
+    projection as the modules' ``masked_fill`` (reference ms_deform_attn.py:287-288) -- on the split-arithmetic path as the
+    GEMMs' row mask (its padded rows written as zeros forward, left out of the gradient's sums backward), otherwise with
+    ATen."""
 
     @staticmethod
-    def forward(ctx, x, n, *wb):
+    def forward(ctx, x, mask, n, *wb):
         from . import gemm_bf16x3 as g3
         ws, bs = wb[:n], wb[n:]
         x2 = x.reshape(-1, x.shape[-1])
-        ctx.save_for_backward(*ws)
         ctx.x_shape = x.shape
         # (split-bf16 products on the bf16 matrix cores where asked for: gemm_bf16x3.py; the planes are cached on the weights' own
         #  parameters -- a Function has no module -- and follow them in place)
         ctx.arith = (g3.enabled() and x2.shape[0] >= 1024 and x2.is_contiguous()
                      and all(g3.supported(x2, w.shape[0], w.shape[1]) for w in ws))
+        rm = None if mask is None else mask.reshape(x2.shape[0])
+        ctx.save_for_backward(rm, *ws)
         if ctx.arith:
-            return tuple(g3.linear(w, "self", x2, w, b).view(*x.shape[:-1], w.shape[0]) for w, b in zip(ws, bs))
-        return tuple(torch.addmm(b, x2, w.t()).view(*x.shape[:-1], w.shape[0]) for w, b in zip(ws, bs))
+            return tuple(g3.linear(w, "self", x2, w, b, row_mask=rm).view(*x.shape[:-1], w.shape[0]) for w, b in zip(ws, bs))
+        outs = tuple(torch.addmm(b, x2, w.t()).view(*x.shape[:-1], w.shape[0]) for w, b in zip(ws, bs))
+        if mask is not None:
+            outs = tuple(o.masked_fill(mask[..., None], float(0)) for o in outs)
+        return outs
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *gs):
-        ws = ctx.saved_tensors
+        rm, *ws = ctx.saved_tensors
         gx = None
         for g, w in zip(gs, ws):
             if g is None:
@@ -175,10 +182,12 @@ class _MultiValueProjections(Function):
             g2 = g.reshape(-1, g.shape[-1])
             if ctx.arith and g2.is_contiguous():
                 from . import gemm_bf16x3 as g3
-                gx = g3.linear_input_grad(w, "self", g2, w, accumulate_into=gx)
+                gx = g3.linear_input_grad(w, "self", g2, w, accumulate_into=gx, row_mask=rm)
             else:
+                if rm is not None:
+                    g2 = g2.masked_fill(rm[:, None], 0.0)
                 gx = g2 @ w if gx is None else gx.addmm_(g2, w)
-        return (None if gx is None else gx.view(ctx.x_shape), None) + (None,) * (2 * len(ws))
+        return (None if gx is None else gx.view(ctx.x_shape), None, None) + (None,) * (2 * len(ws))
 
 
 def _frozen_fp32_linear(lin, x):
@@ -192,10 +201,8 @@ def multi_value_projections(modules, source, key_padding_mask=None):
     project for themselves).  Hand the i-th result to ``modules[i](..., value_projected=...)``."""
     if not modules or not all(_frozen_fp32_linear(m.value_proj, source) for m in modules) or not source.requires_grad:
         return None
-    outs = _MultiValueProjections.apply(source, len(modules), *[m.value_proj.weight for m in modules],
+    outs = _MultiValueProjections.apply(source, key_padding_mask, len(modules), *[m.value_proj.weight for m in modules],
                                         *[m.value_proj.bias for m in modules])
-    if key_padding_mask is not None:
-        outs = tuple(o.masked_fill(key_padding_mask[..., None], float(0)) for o in outs)
     return list(outs)
 
 

@@ -785,6 +785,7 @@ class DeformableTransformerEncoderLayer(nn.Module):
 
     fuse_bias_relu = True   # bias + ReLU in the GEMM epilogue: -117 us per layer (scripts/enclayer_profile.py)
     native_attention = True   # frozen fp32 GPU calls without padding: the attention sublayer as one autograd node (encoder_layer.py)
+    native_padded = True      # the same node for calls WITH a padding mask (encoder_layer.padded_applies); False: the modules
 
     def forward_ffn(self, src):
         if (self.fuse_bias_relu and self.activation is F.relu and src.is_cuda and src.dtype == torch.float32
@@ -813,6 +814,10 @@ class DeformableTransformerEncoderLayer(nn.Module):
                 # lets the three gradients of src meet inside its GEMMs (encoder_layer.py)
                 return self.forward_ffn(native.attention_sublayer(self, src, pos, reference_points, spatial_shapes,
                                                                   level_start_index))
+            if (key_padding_mask is not None and self.native_padded
+                    and native.padded_applies(self, src, pos, reference_points, spatial_shapes, key_padding_mask)):
+                return self.forward_ffn(native.attention_sublayer(self, src, pos, reference_points, spatial_shapes,
+                                                                  level_start_index, key_padding_mask=key_padding_mask))
         # (query = src + pos, value = src: handed over as ONE tensor + pos so that the module can treat them as one node)
         src2 = self.self_attn(query=src, query_pos=pos, reference_points=reference_points,
                               value=src, spatial_shapes=spatial_shapes,
