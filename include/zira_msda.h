@@ -71,10 +71,9 @@ int zira_msda_bwd_f32(const float *grad_out, const float *value, const int64_t *
  * back to a float walk of the same tiles), for D = 16 / 64 the tiles are walked with the window's accumulators in
  * registers.  Sparse calls (decoder cross-attention) with D = 32 take "plan + tile accumulate" (csrc/msda_tiles.hip,
  * see the planned entry points below): without a plan from the forward pass this call plans first, the workspace being
- * the plan buffer.  Other sparse calls keep the round-2 entry sort (per-block counting sort of corner contributions,
- * per-tile row sums).
- * `zira_msda_bwd_workspace_bytes` returns the scratch size it needs for these dimensions (75 MB at
- * B=2,S=22223,M=8,D=32,L=4,Q=900,P=4 -- sized for the worst case, about a fifth is touched; 496 MB at Q=S), or 0 when
+ * the plan buffer.  Other sparse calls (D = 16 / 64, or shapes the plan does not take) take the cell walk.
+ * `zira_msda_bwd_workspace_bytes` returns the scratch size of the path the call takes for these dimensions (123 MB at
+ * B=2,S=22223,M=8,D=32,L=4,Q=900,P=4, sized for the worst case; 496 MB at Q=S), or 0 when
  * no workspace path applies (the plain entry point is then the only one).  The workspace is caller-owned DEVICE
  * memory, 16-byte aligned, needs no initialisation and may be reused by later calls on the same stream; with
  * workspace == NULL or too small the call degrades to zira_msda_bwd_f32.  Every element of grad_value,

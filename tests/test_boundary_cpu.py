@@ -44,6 +44,18 @@ def test_host_only_entry_points_work_without_gpu():
     assert lib.zira_msda_fwd_f32(None, None, None, None, None, 1, 1, 1, 32, 1, 1, 1, None, None) == 1
 
 
+def test_workspace_sizes_at_the_model_shapes():
+    """The scratch the model's two MSDA backward calls ask for, pinned: encoder (Q = S, the cell kernels; no plan) and
+    decoder (Q = 900, plan + tile accumulate; the workspace is the plan buffer).  The plan layout reads the device's CU
+    count; without a GPU it assumes 256, which is also the MI355X's, so the same values hold on both machines."""
+    lib = _lib.load()
+    enc, dec = (2, 22223, 8, 32, 4, 22223, 4), (2, 22223, 8, 32, 4, 900, 4)
+    assert lib.zira_msda_bwd_workspace_bytes(*enc) == 495588096
+    assert lib.zira_msda_plan_bytes(*enc) == 0
+    assert lib.zira_msda_bwd_workspace_bytes(*dec) == 123377408
+    assert lib.zira_msda_plan_bytes(*dec) == 123377408
+
+
 def test_cpu_tensors_raise_like_the_reference():
     v = torch.zeros(1, 4, 2, 32)
     sh = torch.tensor([[2, 2]])

@@ -23,6 +23,7 @@ if torch.cuda.is_available():
 
 DEV = "cuda"
 NORTH_STAR_SHAPES = [(100, 167), (50, 84), (25, 42), (13, 21)]
+LARGE_S_SHAPES = [(120, 200), (60, 100), (30, 50), (15, 25)]   # S = 31875: more than the plan takes, sparse D = 32 calls walk
 
 
 def _tol(dtype):
@@ -413,17 +414,21 @@ def test_boundary_errors_match_reference():
 
 
 def test_tiled_and_atomic_backward_agree(oracle):
-    """The default backward is the atomic-free two-kernel path (C ABI zira_msda_bwd_f32_ws);
-    forcing the atomic path (zira_msda_bwd_f32) must give the same three gradients."""
+    """The default backward is the atomic-free workspace path (C ABI zira_msda_bwd_f32_ws: plan + tile accumulate for
+    the sparse D = 32 calls the plan takes, the cell walk for the others); forcing the atomic path (zira_msda_bwd_f32)
+    must give the same three gradients."""
     from ziragroundingdino_amd import _lib
 
     lib = _lib.load()
     for (B, Q, M, D, shapes, P) in [(2, 900, 8, 32, NORTH_STAR_SHAPES, 4),
                                     (1, 100, 4, 32, [(16, 20)], 4),          # BASELINE configs[0]
                                     (3, 131, 5, 16, [(9, 11), (4, 6), (2, 3)], 3),
-                                    (2, 77, 2, 64, [(30, 41), (15, 21)], 8)]:  # LP = 16 / 9 / 16
+                                    (2, 77, 2, 64, [(30, 41), (15, 21)], 8),  # LP = 16 / 9 / 16
+                                    (1, 60, 4, 32, LARGE_S_SHAPES, 4)]:       # beyond the plan: the walk at D = 32
         S = sum(h * w for h, w in shapes)
         assert lib.zira_msda_bwd_workspace_bytes(B, S, M, D, len(shapes), Q, P) > 0
+        if shapes is LARGE_S_SHAPES:
+            assert lib.zira_msda_plan_bytes(B, S, M, D, len(shapes), Q, P) == 0
         value, sh, start, loc, attn, go = _random_case(B, Q, M, D, shapes, P, seed=21, lo=-0.2, hi=1.2)
         t = lambda a: torch.from_numpy(a).to(DEV)
         args = list(map(t, (value, sh, start, loc, attn, go)))
@@ -442,18 +447,24 @@ def test_tiled_and_atomic_backward_agree(oracle):
         torch.testing.assert_close(tiled[2], atomic[2], rtol=1e-4, atol=1e-5 * float(atomic[2].abs().max()))
 
 
-def test_tiled_backward_overwrites_poisoned_grad_value():
-    """grad_value is written exactly once by the tiled path: no dependence on prior contents
+POISON_CASES = [("d16", 16, NORTH_STAR_SHAPES, 4), ("d32", 32, NORTH_STAR_SHAPES, 4), ("d64", 64, NORTH_STAR_SHAPES, 4),
+                ("d32_p5", 32, NORTH_STAR_SHAPES, 5), ("d32_large_s", 32, LARGE_S_SHAPES, 4)]
+
+
+@pytest.mark.parametrize("D,shapes,P", [c[1:] for c in POISON_CASES], ids=[c[0] for c in POISON_CASES])
+def test_tiled_backward_overwrites_poisoned_grad_value(D, shapes, P):
+    """grad_value is written exactly once by the workspace paths: no dependence on prior contents
     (the torch.empty buffer the binding hands over) and no row left unwritten."""
     from ziragroundingdino_amd import _lib
 
     lib = _lib.load()
-    B, Q, M, D, shapes, P = 2, 50, 8, 32, NORTH_STAR_SHAPES, 4
+    B, Q, M = 2, 50, 8
     S = sum(h * w for h, w in shapes)
     value, sh, start, loc, attn, go = _random_case(B, Q, M, D, shapes, P, seed=8)
     t = lambda a: torch.from_numpy(a).to(DEV)
     v, tsh, tst, tloc, tattn, tgo = map(t, (value, sh, start, loc, attn, go))
     n = lib.zira_msda_bwd_workspace_bytes(B, S, M, D, 4, Q, P)
+    assert n > 0
     ws = torch.full((n,), 0xAB, dtype=torch.uint8, device=DEV)          # garbage workspace
     gv = torch.full_like(v, float("nan"))
     gl = torch.full_like(tloc, float("nan"))

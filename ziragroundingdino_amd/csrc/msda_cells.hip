@@ -1,5 +1,5 @@
-// msda_cells.hip -- backward of multi-scale deformable attention for gfx950 (MI355X), dense calls:
-// "cell walk" and LDS accumulate.
+// msda_cells.hip -- backward of multi-scale deformable attention for gfx950 (MI355X): "cell walk" and LDS
+// accumulate.  Serves dense calls, and the sparse calls the plan + tile accumulate path (csrc/msda_tiles.hip) does not take.
 //
 // Arithmetic to match: reference csrc/MsDeformAttn/ms_deform_im2col_cuda.cuh:87-159 (bilinear
 // col2im: grad_value += w_corner * attn * grad_out, grad_attn = <grad_out, sample>, grad_loc from
@@ -28,7 +28,7 @@
 //     gathered rows per sample.
 //   * per sample the walk needs its 16-byte record and one grad_out row gather (8 rows in round 1).
 //
-// Since round 2 the walk (K2 below) serves D = 16 / 64; dense D = 32 calls (the model's) sum the tiles in LDS
+// The walk (K2 below) serves D = 16 / 64 and sparse D = 32 calls; dense D = 32 calls (the model's) sum the tiles in LDS
 // instead -- msda_bwd_accum, further down: the same bin kernel and records, tiles of 15 x 8 pixels, the
 // corner rows added into 64-bit fixed-point accumulators with ds_add_u64 (exact sums, no ordering needed),
 // the walk kept behind it as the float path for non-finite gradients.
@@ -45,14 +45,14 @@
 //                      the tile's runs, counting-sorts the records by (walker, step) in LDS -- a padded
 //                      stream vis[k][walker] of 4-byte words in which all walkers are in the same step at
 //                      the same k -- then walks it with the records 6 and the grad_out rows 3 elements ahead.
-//   K3 msda_bwd_fold   dense calls only: sums the partial rows of split tiles (below).
+//   K3 msda_bwd_fold   behind the walk: sums the partial rows of split tiles (below).
 //
 // Levels differ in samples per pixel by orders of magnitude (every level receives Q*P samples per
 // head; at the encoder shape that is 5 per pixel on the 100 x 167 level and 326 on the 13 x 21
 // one), and a walker is a serial chain.  The geometry is therefore per level, chosen ON THE
 // DEVICE from the int64 level table (the host never reads it: the C ABI only has device
 // pointers; it only knows bounds that follow from S): the segment width shrinks until a tile
-// holds about `vstar` records, and where that is not enough (dense calls) a tile becomes K work
+// holds about `vstar` records, and where that is not enough (busy levels) a tile becomes K work
 // items, each taking 1/K of the tile's records and writing partial rows that K3 adds up.
 // Precondition, as in the reference module (ms_deform_attn.py:284): the levels tile [0, S).
 
@@ -74,17 +74,11 @@
 #ifndef ZIRA_WALK_LPG32
 #define ZIRA_WALK_LPG32 4    // lanes per walker for D = 32 (4: 16 walkers x 8 channels per lane; 8: 8 x 4)
 #endif
-#ifndef ZIRA_WALK_VSTAR_DENSE
-#define ZIRA_WALK_VSTAR_DENSE 1536   // records a work item should hold
+#ifndef ZIRA_WALK_VSTAR
+#define ZIRA_WALK_VSTAR 1536   // records a work item should hold
 #endif
-#ifndef ZIRA_WALK_VSTAR_SPARSE
-#define ZIRA_WALK_VSTAR_SPARSE 384
-#endif
-#ifndef ZIRA_WALK_GRID_DENSE
-#define ZIRA_WALK_GRID_DENSE 2048
-#endif
-#ifndef ZIRA_WALK_GRID_SPARSE
-#define ZIRA_WALK_GRID_SPARSE 4096
+#ifndef ZIRA_WALK_GRID
+#define ZIRA_WALK_GRID 2048
 #endif
 
 #ifndef ZIRA_DENSE_ACCUM
@@ -140,7 +134,7 @@ struct CellGeom {
     unsigned ng, thp;          // walkers per wave (64 / LPG) and pixel rows per tile (ng - 1)
     unsigned twl_max, twl_min; // log2 of the segment width: upper / lower limit of the per-level choice
     unsigned vstar;            // records a work item should hold
-    unsigned split;            // 1: tiles above vstar are split into K work items (dense calls; needs K3)
+    unsigned split;            // 1: tiles above vstar are split into K work items (needs K3); the host always sets 1
     unsigned prows_max;        // partial rows per head the workspace has room for
     unsigned QB, nblk, slice;  // queries per bin block, bin blocks per head, record slots per block
     unsigned ntmax;            // capacity of the tile histogram (>= tiles per head for any level shapes)
@@ -1364,15 +1358,16 @@ inline bool make_geom(int B, int S, int M, int D, int L, int Q, int P, CellGeom 
     G.S = S; G.M = M; G.L = L; G.P = P; G.LP = L * P; G.Q = Q; G.heads = B * M;
     G.ng = 64 / lpg;
     G.thp = G.ng - 1;
-    const bool dense = (unsigned long long)G.heads * Q >= 16 * 4096;
+    // one geometry for every call, sparse or dense: tiles above vstar records are split into work items and folded
+    // (a sparse geometry without splits degenerated on clustered queries; DESIGN_HISTORY.md, "Cell walk for sparse calls")
     G.twl_max = 3;
-    G.twl_min = dense ? 2 : 1;
-    G.vstar = dense ? ZIRA_WALK_VSTAR_DENSE : ZIRA_WALK_VSTAR_SPARSE;
+    G.twl_min = 2;
+    G.vstar = ZIRA_WALK_VSTAR;
     if (use_accum(B, M, D, Q)) {  // one tile shape for all levels; busy levels only get more work items per tile
         G.twl_max = G.twl_min = ZIRA_ACC_TWL;
         G.vstar = ZIRA_ACC_VSTAR;
     }
-    G.split = dense ? 1u : 0u;
+    G.split = 1;
     G.QB = 64;
     while ((unsigned long long)G.QB * G.LP * 4 > 4096 && G.QB > 1) G.QB >>= 1;  // (12-bit index inside a run)
     if ((unsigned long long)G.QB * G.LP * 4 > 4096) return false;
@@ -1386,11 +1381,8 @@ inline bool make_geom(int B, int S, int M, int D, int L, int Q, int P, CellGeom 
     G.ntmax = (unsigned)(((unsigned long long)S * (G.thp + twm - 1)) / (G.thp * twm)) + L;
     // partial rows per head: a split level has about (its records / vstar) work items of thp * tw rows;
     // all levels together hold ~1.3 records per sample.  The device falls back to K = 1 beyond this.
-    G.prows_max = 0;
-    if (G.split) {
-        const unsigned long long items = (3ull * Q * G.LP / 2) / G.vstar + 4ull * L;
-        G.prows_max = (unsigned)(items * G.thp * (1u << G.twl_max) * 2);
-    }
+    const unsigned long long items = (3ull * Q * G.LP / 2) / G.vstar + 4ull * L;
+    G.prows_max = (unsigned)(items * G.thp * (1u << G.twl_max) * 2);
     G.cap = (G.vstar * 5 / 2 + 511) & ~511u;  // padded stream: records x (longest list / mean list)
     if (G.cap > 10240) G.cap = 10240;         // (the walk takes larger shares in several passes)
     G.LPdiv = make_fast_div(G.LP);
@@ -1425,11 +1417,11 @@ int launch_walk(const CellGeom &G, const float *grad_out, const float *value, co
     // one wave per block; the waves of an XCD stride over the work items of its heads
     // (behind the accumulate kernel the launch is normally a no-op: a small grid keeps it cheap, the ticket counters
     // make any grid size correct)
-    const unsigned grid = only_if ? 512u : (G.split ? ZIRA_WALK_GRID_DENSE : ZIRA_WALK_GRID_SPARSE);
+    const unsigned grid = only_if ? 512u : ZIRA_WALK_GRID;
     hipLaunchKernelGGL((msda_bwd_walk<D, LPG>), dim3(grid), dim3(64), lds2, st, grad_out, value, shapes, start,
                        G, desc, region, partial, tickets, gv, gl, ga, only_if);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !G.split) return (int)e;
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(msda_bwd_fold<D>, dim3(1024), dim3(256), 0, st, shapes, start, G, partial, gv);
     return (int)hipGetLastError();
 }
