@@ -36,14 +36,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.h"
+#include "split_arith.h"
 #include "zira_msda.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kC = 256;                     // model width: contraction of the first product, columns of the second
 constexpr int kRows = 128, kThreads = 512;  // rows per block: 4 pairs of waves, 32 rows per pair
@@ -59,46 +56,11 @@ constexpr int kLdsBytes = 2 * kUnit + 2 * 4 * kTBytes;   // 163840: all of the C
 
 enum { MODE_FWD = 0, MODE_BWD = 1 };
 
-__device__ __forceinline__ unsigned pk_f16(float a, float b)
-{
-    f32x2 x = {a, b};
-    f16x2 h = __builtin_convertvector(x, f16x2);   // round to nearest even
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float f16_lo(unsigned p)
-{
-    f16x2 h = __builtin_bit_cast(f16x2, p);
-    return (float)h[0];
-}
-__device__ __forceinline__ float f16_hi(unsigned p)
-{
-    f16x2 h = __builtin_bit_cast(f16x2, p);
-    return (float)h[1];
-}
-
-// the power of two that brings amax into [2^14, 2^15), and its reciprocal (exact); amax = 0 or tiny: 2^100; inf / NaN pass through
-__device__ __forceinline__ void pow2_scale(float amax, float &s, float &inv)
-{
-    int e = (int)((__float_as_uint(amax) >> 23) & 0xFFu);   // amax in [2^(e-127), 2^(e-126))
-    int se = 127 + 14 - (e - 127);                          // biased exponent of the scale
-    se = se > 227 ? 227 : se;                               // <= 2^100: the reciprocal stays a normal number
-    se = se < 1 ? 1 : se;
-    s = __uint_as_float((unsigned)se << 23);
-    inv = __uint_as_float((unsigned)(254 - se) << 23);
-}
-
 // max of the value in lanes l and l ^ 32, in both
 __device__ __forceinline__ float pair_max(float x)
 {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
-// two fp32 -> one packed pair of each plane
-__device__ __forceinline__ void split2(float x, float y, unsigned &p1, unsigned &p2)
-{
-    p1 = pk_f16(x, y);
-    p2 = pk_f16(x - f16_lo(p1), y - f16_hi(p1));   // (exact differences)
 }
 
 // One wave copies 1 KB global -> LDS: lane l's 16 bytes from src + 16 l to LDS byte address dst + 16 l (src, dst wave-uniform).
@@ -187,17 +149,17 @@ __global__ __launch_bounds__(kThreads) void ffn_f16x2_kernel(const float *__rest
                     amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[p][q].x), fabsf(v[p][q].y))), fmaxf(fabsf(v[p][q].z), fabsf(v[p][q].w)));
             amax = pair_max(amax);
             float a_s;
-            pow2_scale(amax, a_s, a_inv);
+            pow2_scale_seq(amax, a_s, a_inv);
 #pragma unroll
             for (int p = 0; p < 8; ++p)
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const float4 lo = v[p][2 * t], hi = v[p][2 * t + 1];
                     unsigned x1[4], x2[4];
-                    split2(lo.x * a_s, lo.y * a_s, x1[0], x2[0]);
-                    split2(lo.z * a_s, lo.w * a_s, x1[1], x2[1]);
-                    split2(hi.x * a_s, hi.y * a_s, x1[2], x2[2]);
-                    split2(hi.z * a_s, hi.w * a_s, x1[3], x2[3]);
+                    split2_f16x2(lo.x * a_s, lo.y * a_s, x1[0], x2[0]);
+                    split2_f16x2(lo.z * a_s, lo.w * a_s, x1[1], x2[1]);
+                    split2_f16x2(hi.x * a_s, hi.y * a_s, x1[2], x2[2]);
+                    split2_f16x2(hi.z * a_s, hi.w * a_s, x1[3], x2[3]);
                     a1[p][t] = __builtin_bit_cast(f16x8, make_uint4(x1[0], x1[1], x1[2], x1[3]));
                     a2[p][t] = __builtin_bit_cast(f16x8, make_uint4(x2[0], x2[1], x2[2], x2[3]));
                 }
@@ -354,11 +316,11 @@ __global__ __launch_bounds__(kThreads) void ffn_f16x2_kernel(const float *__rest
         _Pragma("unroll") for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, fabsf(tv[r]));                                          \
         tmax = pair_max(tmax);                                                                                                    \
         float t_s, t_inv;                                                                                                         \
-        pow2_scale(tmax, t_s, t_inv);                                                                                             \
+        pow2_scale_seq(tmax, t_s, t_inv);                                                                                         \
         f16x8 t1[2], t2[2];                                                                                                       \
         _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                                           \
             unsigned x1[4], x2[4];                                                                                                \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) split2(tv[8 * j + 2 * q] * t_s, tv[8 * j + 2 * q + 1] * t_s, x1[q], x2[q]); \
+            _Pragma("unroll") for (int q = 0; q < 4; ++q) split2_f16x2(tv[8 * j + 2 * q] * t_s, tv[8 * j + 2 * q + 1] * t_s, x1[q], x2[q]); \
             t1[j] = __builtin_bit_cast(f16x8, make_uint4(x1[0], x1[1], x1[2], x1[3]));                                            \
             t2[j] = __builtin_bit_cast(f16x8, make_uint4(x2[0], x2[1], x2[2], x2[3]));                                            \
         }                                                                                                                         \
@@ -459,15 +421,10 @@ __global__ __launch_bounds__(256) void row_scale_kernel(const float *__restrict_
     const int r = blockIdx.x;
     float amax = 0.f;
     for (int c = threadIdx.x; c < cols; c += 256) amax = fmaxf(amax, fabsf(w[r * row_stride + c * col_stride] * (colmul ? colmul[c] : 1.f)));
-    red[threadIdx.x] = amax;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
+    amax = block_amax256(amax, red);
     if (threadIdx.x == 0) {
         float s, i;
-        pow2_scale(red[0], s, i);
+        pow2_scale_seq(amax, s, i);
         scale[r] = s;
         inv[r] = i;
     }
@@ -483,7 +440,7 @@ __device__ __forceinline__ unsigned short plane_of(float x, int plane)
 {
     const unsigned p1 = pk_f16(x, 0.f);
     if (plane == 0) return (unsigned short)(p1 & 0xFFFFu);
-    return (unsigned short)(pk_f16(x - f16_lo(p1), 0.f) & 0xFFFFu);
+    return (unsigned short)(pk_f16(x - f16_lo(p1), 0.f) & 0xFFFFu);   // (split1_f16x2, with the second plane made only when asked for)
 }
 
 // One thread per 16-byte lane piece of the stream.  P(h, k) = p[h * psh + k * psk], Q(n, h) = q[n * qsn + h * qsh].
@@ -536,11 +493,7 @@ __host__ __device__ inline size_t stream_bytes(int F) { return (size_t)kPBytes +
 struct Deal { int blocks, nfull, nsplit, ntail; };
 Deal deal(int M, int nsteps)
 {
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
+    const int cus = zira::cu_count();
     const int rbs = (M + kRows - 1) / kRows, rest = rbs % cus;
     int nsplit = 1;
     while (rest > 0 && nsplit < 4 && rest * nsplit * 2 <= cus && (nsteps / (nsplit * 2)) % 8 == 0) nsplit *= 2;
@@ -562,12 +515,8 @@ template <int MODE>
 int launch(const float *a, const unsigned char *stream, int nsteps, const float *pbias, const float *qinv, const float *qbias, const float *aux,
            unsigned *mask, float *out, int M, void *workspace, hipStream_t st)
 {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_f16x2_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    const hipError_t e = zira::lds_opt_in(ffn_f16x2_kernel<MODE>, kLdsBytes);
+    if (e != hipSuccess) return (int)e;
     Deal d = deal(M, nsteps);
     if (!workspace && d.ntail) {   // no scratch: whole blocks only
         d.nfull += d.ntail; d.blocks = d.nfull; d.ntail = 0; d.nsplit = 1;

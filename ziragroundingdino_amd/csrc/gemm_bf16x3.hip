@@ -28,6 +28,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "launch.h"
+#include "split_arith.h"
 #include "zira_msda.h"
 
 #ifndef ZIRA_G3_CHUNK
@@ -45,36 +47,10 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kBN = 128, kBK = 32, kThreads = 256;
 constexpr int kRow = 80;   // bytes of an LDS row: 32 bf16 + 16 bytes of padding
 
 enum { EPI_BIAS = 0, EPI_BIAS_RELU = 1, EPI_MASK = 2, EPI_ADD = 3 };
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b)
-{
-    f32x2 x = {a, b};
-    bf16x2 h = __builtin_convertvector(x, bf16x2);   // v_cvt_pk_bf16_f32: round to nearest even
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float bf_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float bf_hi(unsigned p) { return __uint_as_float(p & 0xFFFF0000u); }
-
-// four fp32 numbers -> their three bf16 planes, four bf16 (8 bytes) each
-__device__ __forceinline__ void split4(const float4 v, uint2 &p1, uint2 &p2, uint2 &p3)
-{
-    p1.x = pk_bf16(v.x, v.y);
-    p1.y = pk_bf16(v.z, v.w);
-    const float rx = v.x - bf_lo(p1.x), ry = v.y - bf_hi(p1.x), rz = v.z - bf_lo(p1.y), rw = v.w - bf_hi(p1.y);   // exact
-    p2.x = pk_bf16(rx, ry);
-    p2.y = pk_bf16(rz, rw);
-    p3.x = pk_bf16(rx - bf_lo(p2.x), ry - bf_hi(p2.x));   // (the differences are exact, and fit bf16 exactly)
-    p3.y = pk_bf16(rz - bf_lo(p2.y), rw - bf_hi(p2.y));
-}
 
 // The epilogue: accumulator register 4 g + i of block (ni, mi) is C[m][n], m = row (lane & 31) of the block, n = 8 g + 4 (lane >> 5) + i
 template <int MI, int NI, int EPI>
@@ -194,7 +170,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_bf16x3_kernel(const float *_
             p1.x = __float_as_uint(ra[j].x); p1.y = __float_as_uint(ra[j].y); p2.x = __float_as_uint(ra[j].z); p2.y = __float_as_uint(ra[j].w);
             p3 = p1;
 #else
-            split4(ra[j], p1, p2, p3);
+            split4_bf16x3(ra[j], p1, p2, p3);
 #endif
             unsigned char *d = wa + 32 * j * kRow;
             *reinterpret_cast<uint2 *>(d) = p1;
@@ -319,14 +295,9 @@ template <int BM, int EPI>
 int launch(const float *a, const unsigned short *bp, const float *bias, const float *aux, float *c, int M, int N, int K, hipStream_t st)
 {
     const int rt = (M + BM - 1) / BM, ct = N / kBN, per = (rt + 7) / 8;
-    static bool attr_set = false;
     const size_t lds = (size_t)3 * (BM + kBN) * kRow;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_bf16x3_kernel<BM, EPI>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    const hipError_t e = zira::lds_opt_in(gemm_bf16x3_kernel<BM, EPI>, lds);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, EPI>), dim3(8 * per * ct), dim3(kThreads), lds, st, a, bp, bias, aux, c, M, N, K, rt, ct, per);
     return (int)hipGetLastError();
 }

@@ -26,6 +26,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "launch.h"
+#include "split_arith.h"
 #include "zira_msda.h"
 
 #ifndef ZIRA_G2_BM192_MARGIN
@@ -34,43 +36,10 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kBN = 128, kBK = 32, kThreads = 256;
 constexpr int kRow = 80;   // bytes of an LDS row: 32 f16 + 16 bytes of padding
 
 enum { EPI_BIAS = 0, EPI_BIAS_RELU = 1, EPI_MASK = 2, EPI_ADD = 3, EPI_BIAS_GELU = 4, EPI_BIAS_RES = 5 };
-
-__device__ __forceinline__ unsigned pk_f16(float a, float b)
-{
-    f32x2 x = {a, b};
-    f16x2 h = __builtin_convertvector(x, f16x2);   // round to nearest even
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float f16_lo(unsigned p) { return (float)__builtin_bit_cast(f16x2, p)[0]; }
-__device__ __forceinline__ float f16_hi(unsigned p) { return (float)__builtin_bit_cast(f16x2, p)[1]; }
-
-// the power of two that brings amax into [2^14, 2^15), and its reciprocal (exact); amax = 0 or tiny: 2^100
-__device__ __forceinline__ void pow2_scale(float amax, float &s, float &inv)
-{
-    int e = (int)((__float_as_uint(amax) >> 23) & 0xFFu);
-    int se = 127 + 14 - (e - 127);
-    se = se > 227 ? 227 : (se < 1 ? 1 : se);
-    s = __uint_as_float((unsigned)se << 23);
-    inv = __uint_as_float((unsigned)(254 - se) << 23);
-}
-
-// four fp32 numbers (already scaled) -> their two f16 planes, four halves (8 bytes) each
-__device__ __forceinline__ void split4(const float4 v, uint2 &p1, uint2 &p2)
-{
-    p1.x = pk_f16(v.x, v.y);
-    p1.y = pk_f16(v.z, v.w);
-    p2.x = pk_f16(v.x - f16_lo(p1.x), v.y - f16_hi(p1.x));   // (exact differences)
-    p2.y = pk_f16(v.z - f16_lo(p1.y), v.w - f16_hi(p1.y));
-}
 
 // The epilogue: accumulator register 4 g + i of block (ni, mi) is C[m][n], m = row (lane & 31) of the block, n = 8 g + 4 (lane >> 5) + i
 template <int MI, int NI, int EPI>
@@ -207,7 +176,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_f16x2_kernel(const float *__
             pow2_scale(amax, s, inv);
             v.x *= s; v.y *= s; v.z *= s; v.w *= s;
             uint2 p1, p2;
-            split4(v, p1, p2);
+            split4_f16x2(v, p1, p2);
             unsigned char *d = wa + 32 * j * kRow;
             *reinterpret_cast<uint2 *>(d) = p1;
             *reinterpret_cast<uint2 *>(d + BM * kRow) = p2;
@@ -272,23 +241,16 @@ __global__ __launch_bounds__(256) void split_f16x2_kernel(const float *__restric
     auto at = [&](int k) { return transpose ? w[(size_t)k * cols + n] : w[(size_t)n * cols + k]; };
     float amax = 0.f;
     for (int k = threadIdx.x; k < K; k += 256) amax = fmaxf(amax, fabsf(at(k)));
-    red[threadIdx.x] = amax;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
     float s, inv;
-    pow2_scale(red[0], s, inv);
+    pow2_scale(block_amax256(amax, red), s, inv);
     if (threadIdx.x == 0) winv[n] = inv;
     const int Kp = (K + kBK - 1) / kBK * kBK;              // rows padded with zeros to whole K steps
     const size_t total = (size_t)N * Kp;
     for (int k = threadIdx.x; k < Kp; k += 256) {
         const float v = k < K ? at(k) * s : 0.f;
-        const unsigned p1 = pk_f16(v, 0.f);
-        const unsigned p2 = pk_f16(v - f16_lo(p1), 0.f);
-        planes[(size_t)n * Kp + k] = (unsigned short)(p1 & 0xFFFFu);
-        planes[total + (size_t)n * Kp + k] = (unsigned short)(p2 & 0xFFFFu);
+        const uint2 p = split1_f16x2(v);
+        planes[(size_t)n * Kp + k] = (unsigned short)(p.x & 0xFFFFu);
+        planes[total + (size_t)n * Kp + k] = (unsigned short)(p.y & 0xFFFFu);
     }
 }
 
@@ -297,14 +259,9 @@ int launch(const float *a, const unsigned short *bp, const float *winv, const fl
            float *c, int M, int N, int K, hipStream_t st)
 {
     const int rt = (M + BM - 1) / BM, ct = (N + kBN - 1) / kBN, per = (rt + 7) / 8;
-    static bool attr_set = false;
     const size_t lds = (size_t)2 * (BM + kBN) * kRow + (size_t)BM * sizeof(float);
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16x2_kernel<BM, EPI>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    const hipError_t e = zira::lds_opt_in(gemm_f16x2_kernel<BM, EPI>, lds);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((gemm_f16x2_kernel<BM, EPI>), dim3(8 * per * ct), dim3(kThreads), lds, st, a, bp, winv, bias, aux, rscale, rps, c, M, N, K, rt, ct,
                        per);
     return (int)hipGetLastError();

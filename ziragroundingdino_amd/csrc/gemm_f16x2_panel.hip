@@ -16,36 +16,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "split_arith.h"
 #include "zira_msda.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kRows = 32, kThreads = 256;
 
 enum { EPI_BIAS = 0, EPI_BIAS_RELU = 1, EPI_MASK = 2, EPI_ADD = 3 };
-
-__device__ __forceinline__ unsigned pk_f16(float a, float b)
-{
-    f32x2 x = {a, b};
-    f16x2 h = __builtin_convertvector(x, f16x2);
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float f16_lo(unsigned p) { return (float)__builtin_bit_cast(f16x2, p)[0]; }
-__device__ __forceinline__ float f16_hi(unsigned p) { return (float)__builtin_bit_cast(f16x2, p)[1]; }
-
-__device__ __forceinline__ void pow2_scale(float amax, float &s, float &inv)
-{
-    int e = (int)((__float_as_uint(amax) >> 23) & 0xFFu);
-    int se = 127 + 14 - (e - 127);
-    se = se > 227 ? 227 : (se < 1 ? 1 : se);
-    s = __uint_as_float((unsigned)se << 23);
-    inv = __uint_as_float((unsigned)(254 - se) << 23);
-}
 
 // KS = K / 16 matrix-core steps.  LDS: planes [2][KS][2 halves of a step][32 rows][8 halves] = 2 KS KB, then 32 floats (1 / scale).
 // MASKED (EPI_BIAS / EPI_ADD only): row_mask[m] != 0 marks row m as padding, whose product is absent -- EPI_BIAS writes zeros
@@ -112,12 +90,8 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x2_panel_kernel(const flo
         unsigned char *dst = planes + ((c >> 2) * 2 + ((c >> 1) & 1)) * 512 + row * 16 + (c & 1) * 8;
 #pragma unroll
         for (int j = 0; j < J; ++j) {
-            const float x = v[j].x * s, y = v[j].y * s, z = v[j].z * s, w = v[j].w * s;
             uint2 p1, p2;
-            p1.x = pk_f16(x, y);
-            p1.y = pk_f16(z, w);
-            p2.x = pk_f16(x - f16_lo(p1.x), y - f16_hi(p1.x));
-            p2.y = pk_f16(z - f16_lo(p1.y), w - f16_hi(p1.y));
+            split4_f16x2(make_float4(v[j].x * s, v[j].y * s, v[j].z * s, v[j].w * s), p1, p2);
             *reinterpret_cast<uint2 *>(dst + (2 * j) * 1024) = p1;
             *reinterpret_cast<uint2 *>(dst + (2 * j) * 1024 + KS * 1024) = p2;
         }
@@ -208,24 +182,15 @@ __global__ __launch_bounds__(256) void split_f16x2_frag_kernel(const float *__re
     auto at = [&](int k) { return transpose ? w[(size_t)k * cols + n] : w[(size_t)n * cols + k]; };
     float amax = 0.f;
     for (int k = threadIdx.x; k < K; k += 256) amax = fmaxf(amax, fabsf(at(k)));
-    red[threadIdx.x] = amax;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
     float s, inv;
-    pow2_scale(red[0], s, inv);
+    pow2_scale(block_amax256(amax, red), s, inv);
     if (threadIdx.x == 0) winv[n] = inv;
     const int KS = K / 16, t = n >> 5, lm = n & 31;
     for (int k = threadIdx.x; k < K; k += 256) {
-        const float v = at(k) * s;
-        const unsigned p1 = pk_f16(v, 0.f);
-        const unsigned p2 = pk_f16(v - f16_lo(p1), 0.f);
-        const int st = k >> 4, hf = (k >> 3) & 1, e = k & 7;
-        const size_t base = (((size_t)t * KS + st) * 2) * 512 + (size_t)(hf * 32 + lm) * 8 + e;   // in halves; plane 1 is 512 halves on
-        frags[base] = (unsigned short)(p1 & 0xFFFFu);
-        frags[base + 512] = (unsigned short)(p2 & 0xFFFFu);
+        const uint2 p = split1_f16x2(at(k) * s);
+        const size_t base = frag_offset(t, lm, k, KS);
+        frags[base] = (unsigned short)(p.x & 0xFFFFu);
+        frags[base + 512] = (unsigned short)(p.y & 0xFFFFu);
     }
 }
 

@@ -1,0 +1,58 @@
+// launch.h -- per-device launch state shared by the launchers: the dynamic-LDS opt-in and the CU count.  Both are kept per
+// device (the current one at the call), so a process that drives several devices opts in and sizes its work on each.
+#ifndef ZIRA_LAUNCH_H_
+#define ZIRA_LAUNCH_H_
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include <map>
+#include <mutex>
+#include <utility>
+
+namespace zira {
+
+// Lets `kernel` launch with `bytes` of dynamic LDS on the current device.  48 KB or less needs no opt-in; above that,
+// hipFuncSetAttribute is called only when the launch needs more than the largest size opted in before for this (device,
+// kernel).  Thread-safe.  Returns the runtime's error, if any; the size is then not recorded.
+inline hipError_t lds_opt_in(const void *kernel, size_t bytes)
+{
+    if (bytes <= 48 * 1024) return hipSuccess;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> opted;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &have = opted[{dev, kernel}];
+    if (bytes <= have) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) have = bytes;
+    return e;
+}
+
+template <typename F>
+inline hipError_t lds_opt_in(F *kernel, size_t bytes)
+{
+    return lds_opt_in(reinterpret_cast<const void *>(kernel), bytes);
+}
+
+// The current device's number of CUs, cached per device (256, an MI355X's, where the runtime gives no answer).
+inline int cu_count()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    static std::mutex mu;
+    static std::map<int, int> cus;
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = cus.find(dev);
+    if (it != cus.end()) return it->second;
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev] = n;
+    return n;
+}
+
+}  // namespace zira
+
+#endif  // ZIRA_LAUNCH_H_

@@ -19,34 +19,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lane_sum.h"
 #include "zira_msda.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x)
-{
-    return x + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, 0xf, 0xf, false));
-}
-
-// sum over the G = 32 or 64 lanes of a group (aligned in the wave); every lane ends with the total
-template <int G>
-__device__ __forceinline__ float group_sum(float x)
-{
-    x = dpp_add<0xB1>(x);   // quad_perm:[1,0,3,2]
-    x = dpp_add<0x4E>(x);   // quad_perm:[2,3,0,1]
-    x = dpp_add<0x141>(x);  // row_half_mirror
-    x = dpp_add<0x140>(x);  // row_mirror
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    if (G == 64) {
-        const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        x = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-    }
-    return x;
-}
 
 // One row per group of G lanes; lane j of the group holds the float4s j, j + G, ... (NV of them) of the row.
 template <int G, int NV>
@@ -89,7 +67,7 @@ __global__ __launch_bounds__(kThreads) void ln_fwd_rows(
             }
             s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
         }
-        const float mu = group_sum<G>(s) * inv_c;
+        const float mu = lane_sum<G>(s) * inv_c;
         float q = 0.f;
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
@@ -99,7 +77,7 @@ __global__ __launch_bounds__(kThreads) void ln_fwd_rows(
                 q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
             }
         }
-        const float var = group_sum<G>(q) * inv_c;
+        const float var = lane_sum<G>(q) * inv_c;
         const float rs = rsqrtf(var + eps);
         float4 *yr = reinterpret_cast<float4 *>(y + r * C);
 #pragma unroll
@@ -161,8 +139,8 @@ __global__ __launch_bounds__(kThreads) void ln_bwd_rows(
             s1 += (g[k].x + g[k].y) + (g[k].z + g[k].w);
             s2 += (g[k].x * xh[k].x + g[k].y * xh[k].y) + (g[k].z * xh[k].z + g[k].w * xh[k].w);
         }
-        const float m1 = group_sum<G>(s1) * inv_c;
-        const float m2 = group_sum<G>(s2) * inv_c;
+        const float m1 = lane_sum<G>(s1) * inv_c;
+        const float m2 = lane_sum<G>(s2) * inv_c;
         float4 *dr = reinterpret_cast<float4 *>(dx + r * C);
 #pragma unroll
         for (int k = 0; k < NV; ++k) {

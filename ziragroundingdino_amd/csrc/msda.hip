@@ -306,7 +306,7 @@ __global__ __launch_bounds__(kBlock, 8) void msda_fwd_lean(
 // DPP quad permutes / row mirrors inside a 16-lane row.  Each dot product travels back to the
 // lane that owns the (sample, corner) entry with one ds_bpermute; the four corners of a
 // sample are then combined with two more quad permutes.
-// (sum_over_row_lanes, chunk_dots, store_sample_grads and bwd_home_item: csrc/msda_fwd_lean.h, shared with the fused
+// (chunk_dots, store_sample_grads and bwd_home_item: csrc/msda_fwd_lean.h, shared with the fused
 // home + accumulate launch of csrc/msda_tiles.hip)
 
 // Only kScatter = true is launched (kScatter = false would be the gather half alone: grad_sampling_loc and

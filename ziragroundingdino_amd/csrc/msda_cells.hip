@@ -60,6 +60,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "lane_sum.h"
+#include "launch.h"
 #include "msda_internal.h"
 
 #ifndef ZIRA_WALK_DF
@@ -458,23 +460,6 @@ __global__ __launch_bounds__(kBinThreads) void msda_bwd_bin(
 // ------------------------------------------------------------------------------------------
 // K2: walk
 // ------------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x)
-{
-    return x + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, 0xf, 0xf, false));
-}
-
-// sum over the LPG (4, 8 or 16) consecutive lanes of a walker; every lane gets the total
-template <int LPG>
-__device__ __forceinline__ float group_sum(float x)
-{
-    x = dpp_add<0xB1>(x);                  // quad_perm:[1,0,3,2]
-    x = dpp_add<0x4E>(x);                  // quad_perm:[2,3,0,1]
-    if (LPG >= 8) x = dpp_add<0x141>(x);   // row_half_mirror
-    if (LPG >= 16) x = dpp_add<0x140>(x);  // row_mirror
-    return x;
-}
-
 // lane (8 g + j) <- lane (8 g + I): `row_newbcast` broadcasts one lane of every 16-lane row; the two halves of a
 // row take different source lanes, selected with the bank mask (banks = 4 lanes)
 template <unsigned I>
@@ -850,9 +835,9 @@ __global__ __launch_bounds__(64, ZIRA_WALK_MINWAVES) void msda_bwd_walk(
                     ga = fmaf(__fmul_rn(lh, lw), p11, ga);
                     float gx = fmaf(hh, __fsub_rn(p01, p00), __fmul_rn(lh, __fsub_rn(p11, p10)));
                     float gy = fmaf(hw, __fsub_rn(p10, p00), __fmul_rn(lw, __fsub_rn(p11, p01)));
-                    ga = group_sum<LPG>(ga);
-                    gx = group_sum<LPG>(gx);
-                    gy = group_sum<LPG>(gy);
+                    ga = lane_sum<LPG>(ga);
+                    gx = lane_sum<LPG>(gx);
+                    gy = lane_sum<LPG>(gy);
                     if (j == 0) {
                         const unsigned q = e.rc.x & ((1u << kQBits) - 1);
                         const unsigned pp = (e.rc.x >> kQBits) & ((1u << kPBits) - 1);
@@ -1240,9 +1225,9 @@ __global__ __launch_bounds__(NTHR, ZIRA_ACC_MINW) void msda_bwd_accum(
                 ga = fmaf(w11, p11, ga);
                 float gx = fmaf(hh, __fsub_rn(p01, p00), __fmul_rn(lh, __fsub_rn(p11, p10)));
                 float gy = fmaf(hw, __fsub_rn(p10, p00), __fmul_rn(lw, __fsub_rn(p11, p01)));
-                ga = group_sum<LPS>(ga);
-                gx = group_sum<LPS>(gx);
-                gy = group_sum<LPS>(gy);
+                ga = lane_sum<LPS>(ga);
+                gx = lane_sum<LPS>(gx);
+                gy = lane_sum<LPS>(gy);
                 const unsigned oi = bcast8<i>(cur.oi);
                 if (j == 0) {
                     ga_h[oi] = ga;
@@ -1460,13 +1445,8 @@ int cells_backward_f32(const float *grad_out, const float *value, const int64_t 
     if (accum) {
         const size_t lds = accum_lds_bytes(G, D);
         if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-        static bool attr_set = false;
-        if (!attr_set) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_bwd_accum<32, ZIRA_ACC_THREADS>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
-        }
+        e = lds_opt_in(msda_bwd_accum<32, ZIRA_ACC_THREADS>, 160 * 1024);
+        if (e != hipSuccess) return (int)e;
         const unsigned per_cu = (unsigned)((160 * 1024) / lds), by_threads = 2048 / ZIRA_ACC_THREADS;
         const unsigned bpc = per_cu < by_threads ? per_cu : by_threads;
         hipLaunchKernelGGL((msda_bwd_accum<32, ZIRA_ACC_THREADS>), dim3(256 * (bpc ? bpc : 1)), dim3(ZIRA_ACC_THREADS), lds, st,

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lane_sum.h"
+
 #ifndef ZIRA_K1_GATHERS
 #define ZIRA_K1_GATHERS 8   // row gathers a wave keeps in flight in chunk_dots
 #endif
@@ -15,12 +17,6 @@
 namespace {
 
 constexpr unsigned kLeanWavesPerBlock = 4;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x)
-{
-    return x + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, 0xf, 0xf, false));
-}
 
 struct ItemId {
     unsigned item;  // flat (b, q, m)
@@ -180,16 +176,6 @@ __device__ __forceinline__ void fwd_lean_item(const float *__restrict__ value, c
 // ---- the gather half of the backward: grad_sampling_loc and grad_attn_weight of one (b, q, m) item by one wave ----
 // (reference ms_deform_im2col_cuda.cuh:123-158; the four corner rows of a sample are gathered as in the forward and dotted
 //  with the query's grad_out row)
-template <int CQ>
-__device__ __forceinline__ float sum_over_row_lanes(float x)
-{
-    x = dpp_add<0xB1>(x);                 // quad_perm:[1,0,3,2]   (xor 1)
-    x = dpp_add<0x4E>(x);                 // quad_perm:[2,3,0,1]   (xor 2)
-    if (CQ >= 8) x = dpp_add<0x141>(x);   // row_half_mirror       (xor 4 on quad sums)
-    if (CQ >= 16) x = dpp_add<0x140>(x);  // row_mirror            (xor 8 on octet sums)
-    return x;
-}
-
 // <grad_out row, value row> for the 64 entries of a chunk; entry e's result lands in lane e.
 template <int CQ>
 __device__ __forceinline__ float chunk_dots(const float *__restrict__ vb, const Entry &k,
@@ -221,7 +207,7 @@ __device__ __forceinline__ float chunk_dots(const float *__restrict__ vb, const 
             d = fmaf(v[j].y, g4.y, d);
             d = fmaf(v[j].z, g4.z, d);
             d = fmaf(v[j].w, g4.w, d);
-            d = sum_over_row_lanes<CQ>(d);
+            d = lane_sum<CQ>(d);
             const float t = __int_as_float(__builtin_amdgcn_ds_bpermute(back, __float_as_int(d)));
             if (lane / SLOTS == j0 + j) mine = t;
         }
@@ -315,8 +301,8 @@ __device__ __forceinline__ void bwd_home_item2(const float *__restrict__ grad_ou
             d0 = fmaf(v0[j].y, g0.y, d0); d1 = fmaf(v1[j].y, g1.y, d1);
             d0 = fmaf(v0[j].z, g0.z, d0); d1 = fmaf(v1[j].z, g1.z, d1);
             d0 = fmaf(v0[j].w, g0.w, d0); d1 = fmaf(v1[j].w, g1.w, d1);
-            d0 = sum_over_row_lanes<CQ>(d0);
-            d1 = sum_over_row_lanes<CQ>(d1);
+            d0 = lane_sum<CQ>(d0);
+            d1 = lane_sum<CQ>(d1);
             const float t0 = __int_as_float(__builtin_amdgcn_ds_bpermute(back, __float_as_int(d0)));
             const float t1 = __int_as_float(__builtin_amdgcn_ds_bpermute(back, __float_as_int(d1)));
             if (lane / SLOTS == j) { m0 = t0; m1 = t1; }

@@ -60,6 +60,7 @@
 #include <type_traits>
 
 #include "dev/stamps.h"
+#include "launch.h"
 #include "msda_fwd_lean.h"
 #include "msda_internal.h"
 
@@ -874,19 +875,6 @@ struct TilesLayout {
     unsigned units, grid;
 };
 
-inline unsigned tiles_cu_count()
-{
-    static unsigned cus = 0;  // one device per process (one process per GPU)
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;  // MI355X
-        cus = (unsigned)n;
-    }
-    return cus;
-}
-
 inline bool make_tiles_layout(int B, int S, int M, int D, int L, int Q, int P, TilesLayout &T)
 {
     if (D != 32 || L > (int)kTMaxLevels) return false;
@@ -914,7 +902,7 @@ inline bool make_tiles_layout(int B, int S, int M, int D, int L, int Q, int P, T
     // accumulate blocks: a group = the heads whose value slices one XCD keeps in its L2
     G.ng = heads >= 8 ? 8u : 1u;
     G.hp = G.ng > 1 ? (unsigned)((heads + 7) / 8) : G.heads;
-    T.grid = tiles_cu_count() * ZIRA_TILE_BLOCKS_PER_CU;
+    T.grid = (unsigned)cu_count() * ZIRA_TILE_BLOCKS_PER_CU;
     T.grid &= ~7u;
     if (T.grid < 8 || T.grid < G.ng) return false;
     G.nbg = T.grid / G.ng;
@@ -940,18 +928,14 @@ inline bool make_tiles_layout(int B, int S, int M, int D, int L, int Q, int P, T
     return true;
 }
 
-// Dynamic LDS above 48 KB is an opt-in on runtimes that enforce the default limit (the plan kernels take up to 78 KB, 77 KB
-// at the decoder shape): declared once per kernel; a refusal turns the planned path off (-1: the callers fall back).
+// The plan kernels take up to 78 KB of dynamic LDS (77 KB at the decoder shape), an opt-in above 48 KB; a refusal turns the
+// planned path off (-1: the callers fall back).
 template <typename K>
-inline bool allow_lds(K kernel, size_t bytes, bool &done)
+inline bool allow_lds(K *kernel)
 {
-    if (done || bytes <= 48 * 1024) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    done = true;
-    return true;
+    if (lds_opt_in(kernel, 78 * 1024) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
 }
 
 inline PlanPtrs plan_ptrs(const TilesLayout &T, void *plan)
@@ -981,8 +965,7 @@ int tiles_plan_f32(const int64_t *shapes, const int64_t *start, const float *loc
     TilesLayout T;
     if (!make_tiles_layout(B, S, M, D, L, Q, P, T) || !plan || plan_bytes < T.total || ((uintptr_t)plan & 15)) return -1;
     const PlanPtrs W = plan_ptrs(T, plan);
-    static bool lds_one = false, lds_two = false;   // (one device per process)
-    if (!(T.one_pass ? allow_lds(msda_plan<true>, 78 * 1024, lds_one) : allow_lds(msda_plan<false>, 78 * 1024, lds_two))) return -1;
+    if (!(T.one_pass ? allow_lds(msda_plan<true>) : allow_lds(msda_plan<false>))) return -1;
     if (T.one_pass)
         hipLaunchKernelGGL(msda_plan<true>, dim3(T.units), dim3(kPlanThreads), T.lds_plan, st, shapes, start, loc, attn, T.G, W);
     else
@@ -997,8 +980,7 @@ int tiles_fwd_plan_f32(const float *value, const int64_t *shapes, const int64_t 
     if (!make_tiles_layout(B, S, M, D, L, Q, P, T) || !plan || plan_bytes < T.total || ((uintptr_t)plan & 15)) return -1;
     if ((unsigned long long)B * Q * M >= (1ull << 31) || L * P > 64) return -1;
     const PlanPtrs W = plan_ptrs(T, plan);
-    static bool lds_ok = false;
-    if (!allow_lds(msda_fwd_plan, 78 * 1024, lds_ok)) return -1;
+    if (!allow_lds(msda_fwd_plan)) return -1;
     const unsigned nitems = (unsigned)B * Q * M, per = (nitems + 7) >> 3, wpb = kPlanThreads / 64;
     const unsigned units8 = (T.units + 7) & ~7u;
     const unsigned grid = units8 + 8 * ((per + wpb - 1) / wpb);

@@ -30,6 +30,8 @@
 
 #include <type_traits>
 
+#include "lane_sum.h"
+#include "launch.h"
 #include "zira_msda.h"
 
 namespace {
@@ -39,22 +41,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kStage = 2;    // float4s of A a thread loads before it stores them to LDS
 constexpr int kLnbK = 256;   // LayerNorm-backward prologue: the row length it is built for (d_model)
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x)
-{
-    return x + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, 0xf, 0xf, false));
-}
-
-// sum over the 16 lanes of a DPP row; every lane ends with the total
-__device__ __forceinline__ float row16_sum(float x)
-{
-    x = dpp_add<0xB1>(x);   // quad_perm:[1,0,3,2]
-    x = dpp_add<0x4E>(x);   // quad_perm:[2,3,0,1]
-    x = dpp_add<0x141>(x);  // row_half_mirror
-    x = dpp_add<0x140>(x);  // row_mirror
-    return x;
-}
 
 template <int TW> struct WVec;
 template <> struct WVec<1> { typedef float type; };
@@ -177,8 +163,8 @@ __global__ __launch_bounds__(512) void rowgemm_kernel(const zira_rowgemm_args p)
                 const f32x4 gx = g[v] * xh[v];
                 s2 += (gx.x + gx.y) + (gx.z + gx.w);
             }
-            s1 = row16_sum(s1) * inv_k;
-            s2 = row16_sum(s2) * inv_k;
+            s1 = lane_sum<16>(s1) * inv_k;
+            s2 = lane_sum<16>(s2) * inv_k;
             const bool has_row = r < BM, live = row0 + r < p.m;
 #pragma unroll
             for (int v = 0; v < NV; ++v) {
@@ -315,7 +301,7 @@ __global__ __launch_bounds__(512) void rowgemm_kernel(const zira_rowgemm_args p)
                 float s = 0.f;
 #pragma unroll
                 for (int i = 0; i < TW; ++i) s += v[0][i][r];
-                s = row16_sum(s);
+                s = lane_sum<16>(s);
                 if (nl == 0) red[wave * 16 + 4 * kq + r] = s;
             }
             __syncthreads();
@@ -330,7 +316,7 @@ __global__ __launch_bounds__(512) void rowgemm_kernel(const zira_rowgemm_args p)
                     const float dlt = v[0][i][r] - mu[r];
                     q += dlt * dlt;
                 }
-                q = row16_sum(q);
+                q = lane_sum<16>(q);
                 if (nl == 0) red[128 + wave * 16 + 4 * kq + r] = q;
             }
             __syncthreads();
@@ -430,11 +416,7 @@ extern "C" int zira_rowgemm_f32(const zira_rowgemm_args *args, void *stream)
     const size_t lds = (size_t)(bm * (p.k + 4) + 256) * sizeof(float);
     hipStream_t st = static_cast<hipStream_t>(stream);
     auto launch = [&](auto kernel) -> int {
-        if (lds > 48 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return -4;
-        }
+        if (zira::lds_opt_in(kernel, lds) != hipSuccess) return -4;
         hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, p);
         return hipGetLastError() == hipSuccess ? 0 : -4;
     };

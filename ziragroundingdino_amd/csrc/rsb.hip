@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lane_sum.h"
 #include "zira_msda.h"
 
 namespace {
@@ -34,23 +35,6 @@ __device__ __forceinline__ float smooth_l1_zero_grad(float t)
     return fabsf(t) < 1.f ? t : (t > 0.f ? 1.f : -1.f);
 }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x)
-{
-    return x + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, 0xf, 0xf, false));
-}
-// sum over the 64 lanes of a wave; every lane ends with the total
-__device__ __forceinline__ float wave_sum(float x)
-{
-    x = dpp_add<0xB1>(x);   // quad_perm:[1,0,3,2]
-    x = dpp_add<0x4E>(x);   // quad_perm:[2,3,0,1]
-    x = dpp_add<0x141>(x);  // row_half_mirror
-    x = dpp_add<0x140>(x);  // row_mirror
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
 
 // block-wide sum of up to 3 values -> thread 0 writes them to dst[0..NV)
 template <int NV>
@@ -60,7 +44,7 @@ __device__ __forceinline__ void block_sum_store(float (&v)[NV], float *dst)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        const float s = wave_sum(v[i]);
+        const float s = lane_sum<64>(v[i]);
         if (lane == 0) red[i][wave] = s;
     }
     __syncthreads();

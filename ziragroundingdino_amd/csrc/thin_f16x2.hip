@@ -22,35 +22,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "split_arith.h"
 #include "zira_msda.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kRows = 32, kThreads = 256;
-
-__device__ __forceinline__ unsigned pk_f16(float a, float b)
-{
-    f32x2 x = {a, b};
-    f16x2 h = __builtin_convertvector(x, f16x2);   // round to nearest even
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float f16_lo(unsigned p) { return (float)__builtin_bit_cast(f16x2, p)[0]; }
-__device__ __forceinline__ float f16_hi(unsigned p) { return (float)__builtin_bit_cast(f16x2, p)[1]; }
-
-// the power of two that brings amax into [2^14, 2^15), and its reciprocal (exact); amax = 0 or tiny: 2^100
-__device__ __forceinline__ void pow2_scale(float amax, float &s, float &inv)
-{
-    int e = (int)((__float_as_uint(amax) >> 23) & 0xFFu);
-    int se = 127 + 14 - (e - 127);
-    se = se > 227 ? 227 : (se < 1 ? 1 : se);
-    s = __uint_as_float((unsigned)se << 23);
-    inv = __uint_as_float((unsigned)(254 - se) << 23);
-}
 
 struct ThinArgs {
     const float *A, *A2;             // [B][M][K]; A2 = the second source of a concatenated contraction (CAT) or null
@@ -94,12 +71,8 @@ __device__ __forceinline__ void panel_store(const float4 (&v)[KS / 2], int tid, 
     unsigned char *dst = planes + ((c >> 2) * 2 + ((c >> 1) & 1)) * 512 + row * 16 + (c & 1) * 8;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
-        const float x = v[j].x * s, y = v[j].y * s, z = v[j].z * s, w = v[j].w * s;
         uint2 p1, p2;
-        p1.x = pk_f16(x, y);
-        p1.y = pk_f16(z, w);
-        p2.x = pk_f16(x - f16_lo(p1.x), y - f16_hi(p1.x));   // (exact differences)
-        p2.y = pk_f16(z - f16_lo(p1.y), w - f16_hi(p1.y));
+        split4_f16x2(make_float4(v[j].x * s, v[j].y * s, v[j].z * s, v[j].w * s), p1, p2);
         *reinterpret_cast<uint2 *>(dst + (2 * j) * 1024) = p1;
         *reinterpret_cast<uint2 *>(dst + (2 * j) * 1024 + KS * 1024) = p2;
     }
@@ -247,25 +220,16 @@ __global__ __launch_bounds__(256) void thin_split_kernel(const float *__restrict
     const float *wb = w + (size_t)b * N * K;
     float v = 0.f;
     if (n < N && k < K) v = w_is_kn ? wb[(size_t)k * N + n] : wb[(size_t)n * K + k];
-    red[k] = fabsf(v);
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (k < s) red[k] = fmaxf(red[k], red[k + s]);
-        __syncthreads();
-    }
     float s, inv;
-    pow2_scale(red[0], s, inv);
+    pow2_scale(block_amax256(fabsf(v), red), s, inv);
     unsigned short *f = reinterpret_cast<unsigned short *>(frags + (size_t)b * frag_bytes);
     float *winv = reinterpret_cast<float *>(frags + (size_t)b * frag_bytes + (size_t)ntiles * KS * 2048);
     if (k == 0) winv[n] = inv;
     if (k < 16 * KS) {
-        v *= s;
-        const unsigned p1 = pk_f16(v, 0.f);
-        const unsigned p2 = pk_f16(v - f16_lo(p1), 0.f);
-        const int t = n >> 5, lm = n & 31, st = k >> 4, hf = (k >> 3) & 1, e = k & 7;
-        const size_t base = (((size_t)t * KS + st) * 2) * 512 + (size_t)(hf * 32 + lm) * 8 + e;   // in halves; plane 2 is 512 halves on
-        f[base] = (unsigned short)(p1 & 0xFFFFu);
-        f[base + 512] = (unsigned short)(p2 & 0xFFFFu);
+        const uint2 p = split1_f16x2(v * s);
+        const size_t base = frag_offset(n >> 5, n & 31, k, KS);
+        f[base] = (unsigned short)(p.x & 0xFFFFu);
+        f[base + 512] = (unsigned short)(p.y & 0xFFFFu);
     }
 }
 

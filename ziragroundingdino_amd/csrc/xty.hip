@@ -15,6 +15,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "launch.h"
 #include "zira_msda.h"
 
 namespace {
@@ -382,7 +383,7 @@ int zira_xty_f32(const float *X, const float *Y, int B, int N, int a, int b, int
         const int chunk_rows = (((N + kRowsChunks - 1) / kRowsChunks) + 7) & ~7;
         const dim3 grid(kRowsChunks, 4, B);
         const void *fn = a == 128 ? reinterpret_cast<const void *>(&xty_rows128<false>) : reinterpret_cast<const void *>(&xty_rows128<true>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRowsLds) != hipSuccess) return ZIRA_MSDA_EINVAL;
+        if (zira::lds_opt_in(fn, kRowsLds) != hipSuccess) return ZIRA_MSDA_EINVAL;
         if (a == 128) hipLaunchKernelGGL((xty_rows128<false>), grid, dim3(kThreads), kRowsLds, st, X, Y, N, chunk_rows, workspace);
         else hipLaunchKernelGGL((xty_rows128<true>), grid, dim3(kThreads), kRowsLds, st, X, Y, N, chunk_rows, workspace);
         hipError_t e = hipGetLastError();

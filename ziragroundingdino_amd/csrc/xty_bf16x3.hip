@@ -22,42 +22,19 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "launch.h"
+#include "split_arith.h"
 #include "zira_msda.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kThreads = 256, kTok = 32, kTP = 64, kQ = 256;
 constexpr int kStrideP = kTP * 2 + 64, kStrideQ = kQ * 2 + 64;       // bytes per token row of a plane
 constexpr int kPlaneP = kTok * kStrideP, kPlaneQ = kTok * kStrideQ;
 constexpr int kLds = 3 * (kPlaneP + kPlaneQ);                          // 73728 bytes: two blocks per CU
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b)
-{
-    f32x2 x = {a, b};
-    bf16x2 h = __builtin_convertvector(x, bf16x2);   // v_cvt_pk_bf16_f32: round to nearest even
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float bf_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float bf_hi(unsigned p) { return __uint_as_float(p & 0xFFFF0000u); }
-
-// four fp32 numbers -> their three bfloat16 planes, four halves (8 bytes) each
-__device__ __forceinline__ void split4(const float4 v, uint2 &p1, uint2 &p2, uint2 &p3)
-{
-    p1.x = pk_bf16(v.x, v.y);
-    p1.y = pk_bf16(v.z, v.w);
-    const float rx = v.x - bf_lo(p1.x), ry = v.y - bf_hi(p1.x), rz = v.z - bf_lo(p1.y), rw = v.w - bf_hi(p1.y);   // exact
-    p2.x = pk_bf16(rx, ry);
-    p2.y = pk_bf16(rz, rw);
-    p3.x = pk_bf16(rx - bf_lo(p2.x), ry - bf_hi(p2.x));   // (the differences are exact, and fit bfloat16 exactly)
-    p3.y = pk_bf16(rz - bf_lo(p2.y), rw - bf_hi(p2.y));
-}
 
 // 8 tokens x 1 column per lane (the matrix core's operand: lane (i = l % 32, kg = l / 32) holds k = 8 kg .. + 7 of column i) from
 // a row-major [token][column] plane: two transposing reads of 4 tokens x 16 columns per 16-lane group.  `lane_base` = the
@@ -107,7 +84,7 @@ __global__ __launch_bounds__(kThreads, 2) void xty_bf16x3_kernel(const float *__
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             uint2 a, c, d;
-            split4(rp[i], a, c, d);
+            split4_bf16x3(rp[i], a, c, d);
             unsigned char *w = wp + 16 * i * kStrideP;
             *reinterpret_cast<uint2 *>(w) = a;
             *reinterpret_cast<uint2 *>(w + kPlaneP) = c;
@@ -116,7 +93,7 @@ __global__ __launch_bounds__(kThreads, 2) void xty_bf16x3_kernel(const float *__
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             uint2 a, c, d;
-            split4(rq[i], a, c, d);
+            split4_bf16x3(rq[i], a, c, d);
             unsigned char *w = wq + 4 * i * kStrideQ;
             *reinterpret_cast<uint2 *>(w) = a;
             *reinterpret_cast<uint2 *>(w + kPlaneQ) = c;
@@ -249,14 +226,10 @@ extern "C" int zira_xty_bf16x3_f32(const float *P, const float *Q, int B, int N,
     if (((uintptr_t)P | (uintptr_t)Q | (uintptr_t)out | (uintptr_t)workspace) & 15) return -1;
     const int ntiles = tiles_of(n), chunks = chunks_of(B, N, n);
     const int chunk_rows = (((N + chunks - 1) / chunks) + kTok - 1) / kTok * kTok;   // whole slices
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(xty_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return (int)e;
-        attr = true;
-    }
+    hipError_t e = zira::lds_opt_in(xty_bf16x3_kernel, kLds);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(xty_bf16x3_kernel, dim3(chunks * ntiles, B), dim3(kThreads), kLds, st, P, Q, N, n, chunk_rows, chunks, ntiles, workspace);
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(xty_bf16x3_fold, dim3((n * 64 + 15) / 16, B), dim3(kThreads), 0, st, workspace, chunks, ntiles * kTP, n,
                        transpose ? 1 : 0, out);

@@ -83,7 +83,8 @@ def workspace(device, stream: int, M: int, d_ffn: int) -> torch.Tensor:
     key = (device, stream, M, d_ffn)
     ws = _WORKSPACES.get(key)
     if ws is None:
-        n = _lib.load().zira_ffn_f16x2_workspace_bytes(M, d_ffn)
+        with torch.cuda.device(device):   # (the size depends on the device's CU count)
+            n = _lib.load().zira_ffn_f16x2_workspace_bytes(M, d_ffn)
         # (zeroed by a fill KERNEL, not torch.zeros: that may be a memset node when this first call happens inside a graph
         #  capture, and hipMemsetAsync nodes are replayed out of order on ROCm 7.2 -- scripts/repro_memset_graph.py;
         #  only the tickets at the front need the zeros: at most 256 row blocks of the last round, 256 bytes each)
