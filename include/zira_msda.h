@@ -626,6 +626,32 @@ int zira_sine_pos_hw_f32(const void *mask, int B, int H, int W, int F, int norma
                          const float *dim_t_x, float *out, void *stream);
 
 
+/* Row-wise top-k as one launch (csrc/topk.hip).  x [rows, n] fp32 -> out_val / out_idx [rows, k]: the first k entries of a
+ * STABLE DESCENDING sort of each row -- values descending, equal values by ascending index, -0.0 == +0.0, NaN in front of every
+ * number and NaNs equal among themselves (torch.sort(descending=True, stable=True)) -- so the result depends on the input alone:
+ * the same from run to run and under hipGraph replay.  out_val holds the input's bit patterns.
+ * Served: 1 <= k <= 1024, k <= n <= 2^20, 1 <= rows <= 65535; zira_topk_rows_workspace_bytes answers 0 for anything else (host
+ * arithmetic, no GPU needed) and the entry then returns ZIRA_MSDA_EINVAL.  ws: that many bytes on the device; reserved -- the
+ * present kernels keep their state on chip and never touch it.  One launch, no global atomics, no allocation, no host
+ * synchronisation; capturable.  Return 0 or a hipError_t; enqueue only. */
+size_t zira_topk_rows_workspace_bytes(int rows, int n, int k);
+int zira_topk_rows_f32(const float *x, int rows, int n, int k, float *out_val, int64_t *out_idx, void *ws, size_t ws_bytes,
+                       void *stream);
+
+/* The evaluation tail in the same launch (GroundingDINO.dt_inference + detector_postprocess, reference
+ * groundingdino_dual_zero_rep_branch.py:589-602, :634-675): the top-k above over prob.view(B, Q C), and per selected entry
+ *   label = idx % C, q = idx / C;  box of q as (cx - 0.5 w, cy - 0.5 h, cx + 0.5 w, cy + 0.5 h);  x *= img_w, y *= img_h;
+ *   x *= fl(out_w / img_w), y *= fl(out_h / img_h);  x clamped to [0, out_w], y to [0, out_h];  kept when x1 - x0 > 0 and
+ *   y1 - y0 > 0 -- each operation rounded on its own in fp32, the two quotients formed in double and rounded once, as the op
+ *   chain does: bit-identical to it.
+ * prob [B, Q, C] (probabilities, not logits), boxes [B, Q, 4] cxcywh in 0..1, sizes [B, 4] = (img_h, img_w, out_h, out_w) as
+ * floats.  The kept entries are compacted to the front in score order: scores [B, k], labels [B, k], xyxy [B, k, 4];
+ * n_keep [B] = their count; the entries behind them are zero.  boxes and xyxy 16-byte aligned.  Limits, ws and return as
+ * zira_topk_rows_f32 with rows = B, n = Q C. */
+int zira_detections_f32(const float *prob, const float *boxes, int B, int Q, int C, int k, const float *sizes, float *scores,
+                        int64_t *labels, float *xyxy, int32_t *n_keep, void *ws, size_t ws_bytes, void *stream);
+
+
 /* Human-readable build tag, e.g. "zira_msda 0.1 gfx950". Static storage. */
 const char *zira_msda_version(void);
 

@@ -33,6 +33,7 @@ SYMBOLS = (
     "zira_text_side_scratch_floats", "zira_text_prep_fwd_f32", "zira_text_prep_bwd_f32", "zira_text_out_fwd_f32", "zira_text_out_bwd_f32",
     "zira_sine_pos_hw_f32", "zira_box_head_fwd_f32", "zira_box_head_bwd_f32",
     "zira_level_valid_ratios_f32", "zira_encoder_ref_points_f32", "zira_encoder_proposals_f32",
+    "zira_topk_rows_workspace_bytes", "zira_topk_rows_f32", "zira_detections_f32",
     "zira_msda_version", "zira_msda_variant_f32",
 )
 
@@ -228,6 +229,12 @@ def load():
     lib.zira_thin_f16x2_f32.restype = i
     lib.zira_sine_embed_f32.argtypes = [vp, vp, ll, i, i, f32, vp, vp]
     lib.zira_sine_embed_f32.restype = i
+    lib.zira_topk_rows_workspace_bytes.argtypes = [i, i, i]
+    lib.zira_topk_rows_workspace_bytes.restype = sz
+    lib.zira_topk_rows_f32.argtypes = [vp, i, i, i, vp, vp, vp, sz, vp]
+    lib.zira_topk_rows_f32.restype = i
+    lib.zira_detections_f32.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.zira_detections_f32.restype = i
     lib.zira_msda_version.restype = ctypes.c_char_p
     lib.zira_msda_variant_f32.argtypes = [i]
     lib.zira_msda_variant_f32.restype = ctypes.c_char_p

@@ -135,7 +135,9 @@ class _SelectDecodePiece(torch.nn.Module):
         text_dict = {"encoded_text": memory_text, "text_token_mask": text_token_mask}
         hs, refs, hs_enc, ref_enc, init_box = self.transformer.select_and_decode(
             memory, mask_flatten, lvl_pos, self.shapes, self.spatial_shapes, self.level_start_index,
-            valid_ratios, text_dict, no_padding=self.no_padding, sort_for_topk=True)  # topk faults on replay
+            valid_ratios, text_dict, no_padding=self.no_padding, sort_for_topk=True)
+        # (torch.topk faults on replay: the stable sort stands in for it here; with Switches.native_topk the native
+        #  selection runs instead, the same kernel and the same indices as on the eager path)
         self.n_hs, self.n_refs = len(hs), len(refs)
         return (*hs, *refs, hs_enc, ref_enc, init_box)
 

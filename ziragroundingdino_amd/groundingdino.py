@@ -448,8 +448,20 @@ class GroundingDINO(nn.Module):
     def postprocess(self, box_cls, box_pred, batched_inputs, image_sizes):
         """The evaluation tail of ``forward`` (reference :589-602): top-k detections per image, rescaled to the
         requested output size, clipped, empty boxes dropped."""
+        from . import topk
         from .structures import detector_postprocess
+        from .transformer import Switches
 
+        k = self.select_box_nums_for_evaluation
+        if Switches.native_detections and topk.detections_supported(box_cls, box_pred, k):
+            # one launch for the batch and one host read (the counts) instead of ~25 launches and a sync per image
+            out_sizes = [(inp.get("height", s[0]), inp.get("width", s[1])) for inp, s in zip(batched_inputs, image_sizes)]
+            sizes = self._detection_sizes(image_sizes, out_sizes, box_cls.device)
+            if sizes is not None:
+                scores, labels, xyxy, n_keep = topk.detections(box_cls.sigmoid(), box_pred, k, sizes)
+                return [{"instances": Instances(osize, pred_boxes=Boxes(xyxy[b, :n]), scores=scores[b, :n],
+                                                pred_classes=labels[b, :n])}
+                        for b, (n, osize) in enumerate(zip(n_keep.tolist(), out_sizes))]
         results = self.dt_inference(box_cls, box_pred, image_sizes)
         processed = []
         for r, inp, image_size in zip(results, batched_inputs, image_sizes):
@@ -588,6 +600,19 @@ class GroundingDINO(nn.Module):
         t = self._pixel_stats.get(key)
         if t is None:
             t = self._pixel_stats[key] = torch.as_tensor([w, h, w, h], dtype=torch.float, device=self.device)
+        return t
+
+    def _detection_sizes(self, image_sizes, out_sizes, device):
+        """[B, 4] = (img_h, img_w, out_h, out_w) for ``topk.detections``, uploaded once per distinct tuple of sizes; None
+        where fp32 cannot hold a size exactly (the op chain scales by the Python numbers)."""
+        rows = tuple((float(ih), float(iw), float(oh), float(ow)) for (ih, iw), (oh, ow) in zip(image_sizes, out_sizes))
+        key = ("detection_sizes", rows, str(device))
+        t = self._pixel_stats.get(key)
+        if t is None:
+            t = torch.tensor(rows, dtype=torch.float32)
+            if t.double().tolist() != [list(r) for r in rows] or not bool((t > 0).all()):
+                return None
+            t = self._pixel_stats[key] = t.to(device)
         return t
 
     def preprocess_image(self, batched_inputs):

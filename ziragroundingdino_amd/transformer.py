@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
+from . import topk
 from .dense import (LayerNorm, bi_softmax, bi_softmax_supported, fusion_image_side, fusion_image_side_supported, tall_reduce,
                     tall_reduce_nt, wide_matmul, wide_matmul_residual, wide_matmul_residual_supported)
 from .ms_deform_attn import MultiScaleDeformableAttention as MSDeformAttn
@@ -170,6 +171,11 @@ class Switches:
     fused_attention = True   # lean_mha: csrc/attn.hip for fp32 heads of width 32 without attention mask / dropout (the decoder's)
     fused_ffn_backward = True  # frozen FFNs: (gy @ W2) * (h > 0) in one native GEMM (csrc/gemm_drelu.hip) instead of mm + threshold_backward
     sort_for_topk = False    # select_queries: stable sort instead of torch.topk everywhere (developer switch)
+    # select_queries: the selection as ONE native launch whose result depends on the input alone (topk.py: the first k of a
+    # stable descending sort, ties by index), eagerly and inside the decoder's graph alike.  Off by default: the eager path
+    # keeps torch.topk's own order of tied logits, the one the full-size parity tests inject the reference's order through.
+    native_topk = False
+    native_detections = True   # GroundingDINO.postprocess: the evaluation tail as one launch + one host read per batch (topk.py)
     # arithmetic of the frozen FFN products on the image-token rows: "f32" = the library's fp32 GEMMs (+ csrc/gemm_drelu.hip);
     # "bf16x3" = fp32-accurate split-bf16 products on the bf16 matrix cores (csrc/gemm_bf16x3.hip, gemm_bf16x3.py);
     # "f16x2" = the frozen FFN as ONE launch per direction on the f16 matrix cores in fp32 accuracy (csrc/ffn_f16x2.hip,
@@ -1283,7 +1289,8 @@ class Transformer(nn.Module):
         """Two-stage query selection: top-k pixels by max token logit (reference :301-372).
         -> (refpoint_embed, tgt, init_box_proposal, hs_enc, ref_enc).
         ``sort_for_topk``: take the first k of a stable descending sort instead of torch.topk (same
-        indices unless logits tie); torch.topk inside a replayed hipGraph faults on ROCm 7.2."""
+        indices unless logits tie); torch.topk inside a replayed hipGraph faults on ROCm 7.2.
+        ``Switches.native_topk`` replaces both by the native selection (the sort's indices, one launch)."""
         bs = memory.shape[0]
         if self.two_stage_type == "standard":
             output_memory, output_proposals = gen_encoder_output_proposals(memory, mask_flatten, shapes)
@@ -1291,7 +1298,9 @@ class Transformer(nn.Module):
             enc_outputs_class_unselected = self.enc_out_class_embed(output_memory, text_dict)
             topk_logits = enc_outputs_class_unselected.max(-1)[0]
             enc_outputs_coord_unselected = self.enc_out_bbox_embed(output_memory) + output_proposals
-            if sort_for_topk or Switches.sort_for_topk:
+            if Switches.native_topk and topk.supported(topk_logits, self.num_queries):
+                topk_proposals = topk.topk_rows(topk_logits, self.num_queries)[1]
+            elif sort_for_topk or Switches.sort_for_topk:
                 topk_proposals = torch.sort(topk_logits, dim=1, descending=True, stable=True)[1][:, :self.num_queries]
             else:
                 topk_proposals = torch.topk(topk_logits, self.num_queries, dim=1)[1]  # bs, nq (int64)
