@@ -652,6 +652,45 @@ int zira_detections_f32(const float *prob, const float *boxes, int B, int Q, int
                         int64_t *labels, float *xyxy, int32_t *n_keep, void *ws, size_t ws_bytes, void *stream);
 
 
+/* The training tail on the flat gradient bucket as two launches (csrc/optim_tail.hip): L2 norm, clip, AdamW, gradient clear.
+ * The bucket grad [n] fp32 holds the gradients of every trainable tensor back to back (packed: a tensor may start at any offset);
+ * the parameters stay the separate tensors they are and are reached through a device table of segments, in bucket order and
+ * covering [0, n) without gaps; exp_avg / exp_avg_sq [n] fp32 are laid out as the bucket.  The flat index space is cut into
+ * blocks of ZIRA_OPTIM_TAIL_CHUNK elements, one workgroup each, in both kernels; block_segment[b] (device, one int32 per block)
+ * names the segment that holds element b * ZIRA_OPTIM_TAIL_CHUNK.  No atomics, no waiting between workgroups, no allocation, no
+ * host synchronisation: every result is a pure function of the inputs, bit for bit.
+ *
+ * zira_optim_tail_workspace_bytes(n): 8 bytes (one double) per block; 0 where n is not served (n < 1 or n > 2^26; host arithmetic).
+ *
+ * zira_grad_sqnorm_f32: ws[b] = sum of squares of block b's elements, accumulated in double in a fixed order.
+ *
+ * zira_clip_adamw_f32: every workgroup re-adds the partials in one fixed order, so all hold the same total;
+ *   total_norm = (float)sqrt(total);  scale = min(1, (float)max_norm / (total_norm + 1e-6f))  (fp32, as
+ *   clamp(max_norm / (norm + 1e-6), max=1.0) on fp32 tensors; a NaN norm gives a NaN scale);  *norm_out = total_norm.
+ *   do_step != 0, per element, fp32, every operation rounded on its own (torch.optim.AdamW's single-tensor order):
+ *     g = grad * scale;  p *= (float)(1 - lr wd);  m += (float)(1 - beta1) (g - m);  v = v (float)beta2 + (float)(1 - beta2) g g;
+ *     p += (float)(-lr / bc1) (m / (sqrt(v) / (float)bc2_sqrt + (float)eps));  grad = 0
+ *   with lr = lrs[segment.group].  do_step == 0: grad = grad * scale and the norm only (the accumulation iterations).
+ * lrs: n_groups (1..ZIRA_OPTIM_TAIL_MAX_GROUPS) doubles on the HOST, read during the call; bc1 = 1 - beta1^t, bc2 = 1 - beta2^t,
+ * bc2_sqrt = sqrt(bc2) from the caller's step counter.  segments / block_segment: device memory; a group outside [0, n_groups) or
+ * a table that does not tile [0, n) is the caller's error (the kernels never leave a block's own flat range, whatever the table
+ * says).  Pointers need 4-byte alignment only.  Return 0, ZIRA_MSDA_EINVAL or a hipError_t; enqueue only; capturable. */
+#define ZIRA_OPTIM_TAIL_CHUNK 4096
+#define ZIRA_OPTIM_TAIL_MAX_GROUPS 8
+typedef struct zira_optim_segment {
+    void *param;     /* the parameter tensor's data (fp32, contiguous) */
+    int64_t start;   /* its first element's index in the bucket */
+    int64_t numel;
+    int64_t group;   /* learning-rate group */
+} zira_optim_segment;
+size_t zira_optim_tail_workspace_bytes(int64_t n);
+int zira_grad_sqnorm_f32(const float *grad, int64_t n, void *ws, size_t ws_bytes, void *stream);
+int zira_clip_adamw_f32(float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const zira_optim_segment *segments,
+                        int n_segments, const int32_t *block_segment, const double *lrs, int n_groups, double beta1,
+                        double beta2, double eps, double weight_decay, double bc1, double bc2, double bc2_sqrt, double max_norm,
+                        int do_step, float *norm_out, const void *ws, size_t ws_bytes, void *stream);
+
+
 /* Human-readable build tag, e.g. "zira_msda 0.1 gfx950". Static storage. */
 const char *zira_msda_version(void);
 

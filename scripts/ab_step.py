@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Dev: same-box A/B of class-level switches on the replayed training step.  `python scripts/ab_step.py NAME=0|1 ...` with
-NAME in {dummy_launches (N tiny adds per fusion block), gemm_arith (f32|bf16x3), shared_source, batch_value, native_layer, native_glue, native_attention, overlap_text, compose_text, residual_in_gemm, graph_encoder, graph_decoder}: sets the switch, times 40 steps after 8 warm-up steps (graph replay, 4 rotating minibatches),
+NAME in {dummy_launches (N tiny adds per fusion block), gemm_arith (f32|bf16x3), shared_source, batch_value, native_layer, native_glue, native_attention, overlap_text, compose_text, residual_in_gemm, graph_encoder, graph_decoder, native_tail}: sets the switch, times 40 steps after 8 warm-up steps (graph replay, 4 rotating minibatches),
 prints ms per step.  Run the variants alternately in ONE gpurun call, several times each: processes on one box differ by up to
 0.5 ms; two trainers in one process do not work as an A/B (the second one built is 3 ms slower whatever its switches)."""
 import os
@@ -65,6 +65,8 @@ for kv in sys.argv[1:]:
         ZiraTrainer.prefetch_at_start = bool(int(v))
         import faulthandler
         faulthandler.dump_traceback_later(90, exit=True)     # (a hung GPU must not hold the box)
+    elif k == "native_tail":         # norm + clip + AdamW + gradient clear as two native launches (csrc/optim_tail.hip)
+        ZiraTrainer.native_tail = bool(int(v))
     elif k == "frontend_graphs":
         _fg = bool(int(v))
     elif k == "native_pos":

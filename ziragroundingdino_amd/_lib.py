@@ -34,6 +34,7 @@ SYMBOLS = (
     "zira_sine_pos_hw_f32", "zira_box_head_fwd_f32", "zira_box_head_bwd_f32",
     "zira_level_valid_ratios_f32", "zira_encoder_ref_points_f32", "zira_encoder_proposals_f32",
     "zira_topk_rows_workspace_bytes", "zira_topk_rows_f32", "zira_detections_f32",
+    "zira_optim_tail_workspace_bytes", "zira_grad_sqnorm_f32", "zira_clip_adamw_f32",
     "zira_msda_version", "zira_msda_variant_f32",
 )
 
@@ -235,6 +236,14 @@ def load():
     lib.zira_topk_rows_f32.restype = i
     lib.zira_detections_f32.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.zira_detections_f32.restype = i
+    f64 = ctypes.c_double
+    lib.zira_optim_tail_workspace_bytes.argtypes = [ll]
+    lib.zira_optim_tail_workspace_bytes.restype = sz
+    lib.zira_grad_sqnorm_f32.argtypes = [vp, ll, vp, sz, vp]
+    lib.zira_grad_sqnorm_f32.restype = i
+    lib.zira_clip_adamw_f32.argtypes = [vp, vp, vp, ll, vp, i, vp, ctypes.POINTER(f64), i, f64, f64, f64, f64, f64, f64, f64, f64, i,
+                                        vp, vp, sz, vp]
+    lib.zira_clip_adamw_f32.restype = i
     lib.zira_msda_version.restype = ctypes.c_char_p
     lib.zira_msda_variant_f32.argtypes = [i]
     lib.zira_msda_variant_f32.restype = ctypes.c_char_p

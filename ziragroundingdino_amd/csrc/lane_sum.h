@@ -34,6 +34,43 @@ __device__ __forceinline__ float lane_sum(float x)
     return x;
 }
 
+// the same for a double: its two halves travel through the same exchanges
+__device__ __forceinline__ double halves_to_double(unsigned lo, unsigned hi)
+{
+    return __hiloint2double((int)hi, (int)lo);
+}
+
+template <int CTRL>
+__device__ __forceinline__ double dpp_add(double x)
+{
+    const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)__double2loint(x), CTRL, 0xf, 0xf, false);
+    const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)__double2hiint(x), CTRL, 0xf, 0xf, false);
+    return x + halves_to_double(lo, hi);
+}
+
+template <int N>
+__device__ __forceinline__ double lane_sum(double x)
+{
+    static_assert(N == 4 || N == 8 || N == 16 || N == 32 || N == 64, "lane_sum: N is 4, 8, 16, 32 or 64");
+    x = dpp_add<0xB1>(x);
+    x = dpp_add<0x4E>(x);
+    if (N >= 8) x = dpp_add<0x141>(x);
+    if (N >= 16) x = dpp_add<0x140>(x);
+    if (N >= 32) {
+        const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
+        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        x = halves_to_double(a[0], b[0]) + halves_to_double(a[1], b[1]);
+    }
+    if (N == 64) {
+        const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
+        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        x = halves_to_double(a[0], b[0]) + halves_to_double(a[1], b[1]);
+    }
+    return x;
+}
+
 }  // namespace
 
 #endif  // ZIRA_LANE_SUM_H_

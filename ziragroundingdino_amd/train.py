@@ -96,8 +96,34 @@ class ZiraTrainer:
         # the same update rule, element-wise
         fused = self.params[0].is_cuda and self.fused_optimizer
         self.optimizer = torch.optim.AdamW(groups, lr=lr, betas=betas, weight_decay=weight_decay, fused=fused)
+        # the native tail's state over the same tensors and bucket (optim_tail.py); None: the torch path (CPU tensors,
+        # anything ``supported`` declines)
+        self._tail = None
+        if self.native_tail:
+            from . import optim_tail
+
+            if optim_tail.supported(self.params, self.flat_grad):
+                group_of = {id(p): gi for gi, grp in enumerate(self.optimizer.param_groups) for p in grp["params"]}
+                self._tail = optim_tail.NativeOptimTail(self.params, self.flat_grad, [group_of[id(p)] for p in self.params],
+                                                        betas=betas, eps=self.optimizer.defaults["eps"],
+                                                        weight_decay=weight_decay)
 
     fused_optimizer = True   # class-level switch (tests compare with the multi-tensor implementation)
+    # class-level switch: norm + clip + AdamW + gradient clear as two native launches (csrc/optim_tail.hip) instead of the op
+    # chain below, where it serves (L2 clip set, no GradScaler: ``unscale_`` and the inf-skip belong to the scaler).  The
+    # moments then live in ``_tail``, not in ``optimizer.state``: ``export_tail_state()`` before ``optimizer.state_dict()``.
+    native_tail = False
+    last_grad_norm = None    # 0-dim device tensor: the bucket's norm before the clip, of the latest run_step (no host sync)
+
+    def export_tail_state(self):
+        """Copy the native tail's moments and step count into ``self.optimizer.state`` (checkpoints, leaving the native path)."""
+        if self._tail is not None:
+            self._tail.export_to(self.optimizer)
+
+    def import_tail_state(self):
+        """Take moments and step count from ``self.optimizer.state`` (a loaded checkpoint, entering the native path)."""
+        if self._tail is not None:
+            self._tail.import_from(self.optimizer)
 
     def _check_bucket(self):
         """The all-reduce, the clipping and the zeroing act on the flat bucket only: a ``.grad`` that no
@@ -170,19 +196,28 @@ class ZiraTrainer:
             self.flat_grad.div_(self.world)
         if self.on_reduced_grad is not None:
             self.on_reduced_grad(self.flat_grad)
-        if self.clip_max_norm is not None:
-            if scaler is not None:
-                scaler.unscale_(self.optimizer)   # (:187-189; without a clip, scaler.step() unscales)
-            # clip_grad_norm_ over the side-branch tensors == one norm of the flat bucket; every iteration (:188-189, :194-195)
-            total_norm = torch.linalg.vector_norm(self.flat_grad, self.clip_norm_type)
-            self.flat_grad.mul_(torch.clamp(self.clip_max_norm / (total_norm + 1e-6), max=1.0))
-        if self.iter % self.batch_size_scale == 0:   # (:190, :196)
-            if scaler is not None:
-                scaler.step(self.optimizer)
-                scaler.update()
-            else:
-                self.optimizer.step()
-            self.flat_grad.zero_()  # keeps the views alive (no set_to_none)
+        stepping = self.iter % self.batch_size_scale == 0   # (:190, :196)
+        if (self.native_tail and self._tail is not None and self.clip_max_norm is not None and self.clip_norm_type == 2
+                and scaler is None):
+            # the same clip every iteration and step every k-th, as two launches; the learning rates are the torch
+            # optimizer's of this moment (a scheduler acting on it keeps working)
+            self._tail.step([grp["lr"] for grp in self.optimizer.param_groups], do_step=stepping, max_norm=self.clip_max_norm)
+            self.last_grad_norm = self._tail.norm
+        else:
+            if self.clip_max_norm is not None:
+                if scaler is not None:
+                    scaler.unscale_(self.optimizer)   # (:187-189; without a clip, scaler.step() unscales)
+                # clip_grad_norm_ over the side-branch tensors == one norm of the flat bucket; every iteration (:188-189, :194-195)
+                total_norm = torch.linalg.vector_norm(self.flat_grad, self.clip_norm_type)
+                self.flat_grad.mul_(torch.clamp(self.clip_max_norm / (total_norm + 1e-6), max=1.0))
+                self.last_grad_norm = total_norm
+            if stepping:
+                if scaler is not None:
+                    scaler.step(self.optimizer)
+                    scaler.update()
+                else:
+                    self.optimizer.step()
+                self.flat_grad.zero_()  # keeps the views alive (no set_to_none)
         self.iter += 1
         return {k: v.detach() for k, v in loss_dict.items()}
 
