@@ -177,7 +177,9 @@ int zira_attn_fwd_f32(const float *q, const float *k, const float *v, const floa
 /* Gradients of the above: dq [L, B, H*32], dk / dv [S, B, H*32] contiguous, every element written.  `scratch`
  * (16-byte aligned, zira_attn_bwd_scratch_floats() floats; B*H*L is the minimum) holds <dout, out> per query and, when
  * there are few key blocks, the partial dk / dv sums of the shares of the query range, which a third launch adds up in
- * a fixed order (no atomics: the result does not depend on the run). */
+ * a fixed order (no atomics: the result does not depend on the run).  The partial sums start at B*H*L rounded up to a
+ * multiple of 4 floats, and zira_attn_bwd_scratch_floats() counts that rounding: with exactly the reported size the
+ * shares are used; with less (down to B*H*L) the call still succeeds, in one share. */
 size_t zira_attn_bwd_scratch_floats(int L, int S, int B, int H);
 int zira_attn_bwd_f32(const float *q, const float *k, const float *v, const float *key_mask, const float *out,
                       const float *dout, const float *lse, int L, int S, int B, int H, int d, int ldq, int ldk, int ldv,

@@ -63,16 +63,25 @@ def _bad_row_fraction(a, b, tol):
     return float(bad.float().mean())
 
 
+# Seed of the inputs where it is not 0.  (100, 2, 256) at seed 0 puts ONE of the FFN's 409 600 pre-activations at 5.5e-8 (of a
+# largest 3.7): the two sides' fp32 roundings of it fall on either side of the ReLU's kink, where the op is not differentiable,
+# and that query's gradient differs by 1.3e-2 (the native side agrees with a float64 run of the modules to 4e-7 there).
+_SEED = {(100, 2, 256): 1}
+
+
 @pytest.mark.parametrize("Q,B,T,shapes,box_refs", [
     (900, 2, 16, [(25, 34), (13, 17), (7, 9), (4, 5)], True),
     (100, 1, 7, [(12, 10), (6, 5), (3, 3), (2, 2)], True),
     (37, 3, 32, [(16, 16), (8, 8), (4, 4), (2, 2)], False),
+    (100, 2, 194, [(12, 10), (6, 5), (3, 3), (2, 2)], True),   # long caption, seven ragged key tiles (4 query tiles: one share)
+    (100, 2, 256, [(12, 10), (6, 5), (3, 3), (2, 2)], True),   # full-length text: the masked four-wave forward
+    (900, 2, 194, [(12, 10), (6, 5), (3, 3), (2, 2)], True),   # long caption at 900 queries: the text backward in seven shares
 ])
 @pytest.mark.parametrize("frozen_offsets", [False, True])
 def test_native_layer_matches_module_composition(Q, B, T, shapes, box_refs, frozen_offsets):
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
-    layer, x = _setup(Q, B, T, shapes, box_refs=box_refs)
+    layer, x = _setup(Q, B, T, shapes, seed=_SEED.get((Q, B, T), 0), box_refs=box_refs)
     if frozen_offsets:   # offsets = their bias, whatever the query: identical sampling locations on both sides
         with torch.no_grad():
             layer.cross_attn.sampling_offsets.weight.zero_()

@@ -430,7 +430,9 @@ size_t zira_attn_bwd_scratch_floats(int L, int S, int B, int H)
 {
     if (L <= 0 || S <= 0 || B <= 0 || H <= 0) return 0;
     const int qs = dkv_query_shares(L, S, B, H);
-    return (size_t)B * H * L + (qs > 1 ? 2 * (size_t)qs * S * B * H * kD : 0);
+    if (qs == 1) return (size_t)B * H * L;
+    // (the partial sums are read and written as float4: they start at the next multiple of 4 floats behind delta)
+    return (((size_t)B * H * L + 3) / 4) * 4 + 2 * (size_t)qs * S * B * H * kD;
 }
 
 int zira_attn_bwd_f32(const float *q, const float *k, const float *v, const float *key_mask, const float *out,
