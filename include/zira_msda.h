@@ -693,6 +693,28 @@ int zira_clip_adamw_f32(float *grad, float *exp_avg, float *exp_avg_sq, int64_t 
                         int do_step, float *norm_out, const void *ws, size_t ws_bytes, void *stream);
 
 
+/* A minibatch of differently sized images into one fixed canvas, as one launch (csrc/place.hip): the normalised batch tensor
+ * canvas [n_images, 3, Hc, Wc] fp32 -- inside image i's rectangle [0, h_i) x [0, w_i) the value (x - mean[c]) / std[c], zero
+ * elsewhere -- and the padding mask [n_images, Hc, Wc], one byte per pixel (a torch bool tensor), 1 outside the rectangle.
+ * Every element of both is written exactly once; nothing needs to be filled beforehand.  Arithmetic: the source converted to
+ * fp32, one subtract, one correctly rounded IEEE divide, each rounded on its own: the bits of `(x.float() - mean) / std`.
+ * images: n_images (1..ZIRA_PLACE_MAX_IMAGES) descriptors in HOST memory, read during the call and handed to the kernel by value
+ * (no upload, no host synchronisation); data: [3, h, w] on the device, element (c, y, x) at data[c stride_c + y stride_r + x]
+ * (strides in elements, stride_r >= w, channel planes not overlapping), aligned to its element type only; 1 <= h <= Hc,
+ * 1 <= w <= Wc.  The 16-byte stores need Wc % 4 == 0 and a 16-byte aligned canvas (any other canvas is served one pixel per
+ * thread).  _f32: float sources; _u8: unsigned 8-bit sources.  Bytes moved: sum_i 3 h_i w_i sizeof(T) read, n_images Hc Wc 13
+ * written.  Return 0, ZIRA_MSDA_EINVAL or a hipError_t; enqueue only, on `stream`; capturable. */
+#define ZIRA_PLACE_MAX_IMAGES 8
+typedef struct zira_place_image {
+    const void *data;
+    int32_t h, w;
+    int64_t stride_c, stride_r;
+} zira_place_image;
+int zira_place_batch_f32(const zira_place_image *images, int n_images, int Hc, int Wc, float mean0, float mean1, float mean2,
+                         float std0, float std1, float std2, float *canvas, unsigned char *mask, void *stream);
+int zira_place_batch_u8(const zira_place_image *images, int n_images, int Hc, int Wc, float mean0, float mean1, float mean2,
+                        float std0, float std1, float std2, float *canvas, unsigned char *mask, void *stream);
+
 /* Human-readable build tag, e.g. "zira_msda 0.1 gfx950". Static storage. */
 const char *zira_msda_version(void);
 

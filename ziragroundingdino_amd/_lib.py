@@ -35,6 +35,7 @@ SYMBOLS = (
     "zira_level_valid_ratios_f32", "zira_encoder_ref_points_f32", "zira_encoder_proposals_f32",
     "zira_topk_rows_workspace_bytes", "zira_topk_rows_f32", "zira_detections_f32",
     "zira_optim_tail_workspace_bytes", "zira_grad_sqnorm_f32", "zira_clip_adamw_f32",
+    "zira_place_batch_f32", "zira_place_batch_u8",
     "zira_msda_version", "zira_msda_variant_f32",
 )
 
@@ -59,6 +60,15 @@ class RowGemmArgs(ctypes.Structure):
         ("m", ctypes.c_int), ("n", ctypes.c_int), ("k", ctypes.c_int),
         ("batch", ctypes.c_int), ("a_batch_first", ctypes.c_int), ("c_batch_first", ctypes.c_int),
     ]
+
+
+PLACE_MAX_IMAGES = 8
+
+
+class PlaceImage(ctypes.Structure):
+    """``zira_place_image`` of include/zira_msda.h, field for field."""
+    _fields_ = [("data", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("stride_c", ctypes.c_int64), ("stride_r", ctypes.c_int64)]
 
 
 class ExtensionMissingError(ImportError):
@@ -244,6 +254,9 @@ def load():
     lib.zira_clip_adamw_f32.argtypes = [vp, vp, vp, ll, vp, i, vp, ctypes.POINTER(f64), i, f64, f64, f64, f64, f64, f64, f64, f64, i,
                                         vp, vp, sz, vp]
     lib.zira_clip_adamw_f32.restype = i
+    for name in ("zira_place_batch_f32", "zira_place_batch_u8"):
+        f = getattr(lib, name)
+        f.argtypes, f.restype = [ctypes.POINTER(PlaceImage), i, i, i] + [f32] * 6 + [vp, vp, vp], i
     lib.zira_msda_version.restype = ctypes.c_char_p
     lib.zira_msda_variant_f32.argtypes = [i]
     lib.zira_msda_variant_f32.restype = ctypes.c_char_p

@@ -37,15 +37,26 @@ def _clone_tree(obj):
     return obj
 
 
+def _evict_lru(cache, cap):
+    """Drop the least recently used entries of ``cache`` (a dict kept in order of use) until one more fits under ``cap``: the
+    entry's graphs, their memory pools and static buffers go with it.  Called before anything of the new signature has run, and
+    only after the device has finished whatever may still be replaying from the dropped graphs."""
+    torch.cuda.synchronize()
+    while cache and len(cache) >= max(int(cap), 1):
+        del cache[next(iter(cache))]
+
+
 class GraphedNoGrad:
     """fn: tensor-in / tensor-out callable; modules: the nn.Modules it runs (their .training flags are
     part of the cache key); clone_outputs=False hands out the static buffers themselves (valid until
-    the next replay of the same signature only)."""
+    the next replay of the same signature only); evict_lru: at ``max_signatures`` a new signature takes the place of the least
+    recently used one (False: it runs eagerly, and so does every later one)."""
 
-    def __init__(self, fn, modules=(), max_signatures=8, warmup=2, clone_outputs=True):
+    def __init__(self, fn, modules=(), max_signatures=8, warmup=2, clone_outputs=True, evict_lru=False):
         self.fn = fn
         self.modules = tuple(modules)
         self.max_signatures = max_signatures
+        self.evict_lru = evict_lru
         self.warmup = warmup
         self.clone_outputs = clone_outputs
         self._cache = {}
@@ -64,11 +75,15 @@ class GraphedNoGrad:
         key = (tuple((tuple(t.shape), t.dtype, t.device.index) for t in tensors), self._mode_key())
         entry = self._cache.get(key)
         if entry is None:
-            if len(self._cache) >= self.max_signatures:  # unbounded shape variety: stay eager
-                with torch.no_grad():
-                    return self.fn(*args)
+            if len(self._cache) >= self.max_signatures:
+                if not self.evict_lru:                   # unbounded shape variety: stay eager
+                    with torch.no_grad():
+                        return self.fn(*args)
+                _evict_lru(self._cache, self.max_signatures)
             entry = self._capture(args, tensors)
             self._cache[key] = entry
+        elif self.evict_lru:
+            self._cache[key] = self._cache.pop(key)      # most recently used last
         static_in, graph, static_out = entry
         for m in self.modules:      # derived weights (the bf16 planes of the split-bf16 arithmetic) follow their parameters IN PLACE
             refresh = getattr(m, "refresh_derived", None)
@@ -204,7 +219,9 @@ class GraphedTransformer:
     selection takes the first k of a stable descending sort instead: same indices unless logits tie)
     and graphs that contain three or more BiAttention blocks (found by bisection in round 2).
     One set of graphs per input signature (image size / caption length); further signatures
-    run eagerly after ``max_signatures``."""
+    run eagerly after ``max_signatures`` -- or, with ``evict_lru``, take the place of the least recently used set (canvas
+    batching: one set per canvas; eviction is for the task boundary, where the caption length changes).  A signature whose
+    capture was refused (``_eager_keys``) is never retried either way."""
 
     # Class-level switches: which pieces replay from graphs.  The decoder piece is ~1000 launches of a few microseconds: graphed,
     # 36.6-36.7 against 39.6-39.9 ms per step launched eagerly.  The six encoder pieces are ~120 launches for ~4 ms of GPU time
@@ -220,9 +237,10 @@ class GraphedTransformer:
     graph_selection = False  # two-stage query selection runs eagerly with torch.topk -- the indices the eager path and the
                              # reference pick, ties included; True: inside the decoder's graph, as the first k of a stable sort
 
-    def __init__(self, transformer, max_signatures=2):
+    def __init__(self, transformer, max_signatures=2, evict_lru=False):
         self.transformer = transformer
         self.max_signatures = max_signatures
+        self.evict_lru = evict_lru
         self._cache = {}
         self._eager_keys = set()     # signatures whose capture was refused: they run eagerly from then on
         self._versions = None
@@ -268,6 +286,11 @@ class GraphedTransformer:
                torch.is_autocast_enabled("cuda"), torch.get_autocast_dtype("cuda"),   # a capture bakes the dtype path in
                Switches.gemm_arith)                                                    # and the arithmetic of the frozen products
         self._refresh_derived_weights()
+        if self.evict_lru and key not in self._eager_keys:
+            if key in self._cache:
+                self._cache[key] = self._cache.pop(key)       # most recently used last
+            elif len(self._cache) >= self.max_signatures:     # here, before any piece of this step has run
+                _evict_lru(self._cache, self.max_signatures)
         if key in self._eager_keys or (key not in self._cache and len(self._cache) >= self.max_signatures):
             hs, refs, hs_enc, ref_enc, init_box, _ = t(srcs, masks, None, poss, None, None, text_dict,
                                                        no_padding=no_padding)

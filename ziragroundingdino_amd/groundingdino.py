@@ -27,6 +27,7 @@ from torch import nn
 
 from .backbone import build_backbone
 from .bert import BertConfig, BertModel, SimpleTokenizer
+from . import canvas
 from .box_ops import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh
 from .criterion import build_criterion
 from .dense import conv_module_as_gemm
@@ -210,6 +211,44 @@ class GroundingDINO(nn.Module):
         self._text_stream = None
         self._prefetch_stream = None
         self._graphed_transformer = GraphedTransformer(self.transformer)
+        self._canvas_sizes = None
+
+    # Canvas batching (canvas.py), off by default.  None: a minibatch is padded to its own maximum, as the reference does.  A list
+    # of (H, W), e.g. ``canvas.DEFAULT_CANVASES``: it is padded to the smallest canvas that holds it, by one launch, so that a
+    # stream of image sizes meets a handful of shapes and keeps replaying from hipGraphs; the graph caches then hold one entry per
+    # canvas and drop the least recently used one instead of going eager (graphs.py ``evict_lru``).  A batch that no canvas holds
+    # takes the path of None.
+    @property
+    def canvas_sizes(self):
+        return self._canvas_sizes
+
+    @canvas_sizes.setter
+    def canvas_sizes(self, sizes):
+        sizes = None if sizes is None else [(int(h), int(w)) for h, w in sizes]
+        if sizes is not None and not sizes:
+            raise ValueError("canvas_sizes: None or at least one (H, W)")
+        self._canvas_sizes = sizes
+        on = sizes is not None
+        self._graphed_backbone.evict_lru = self._graphed_bert.evict_lru = self._graphed_transformer.evict_lru = on
+        self._graphed_backbone.max_signatures = len(sizes) if on else 8
+        self._graphed_transformer.max_signatures = len(sizes) if on else 2
+
+    def _canvas_batch(self, batched_inputs):
+        """(images, samples) of a minibatch on the canvas ``canvas.choose`` picks for its largest height and width (both known on
+        the host), or (None, None) where no canvas holds it.  ``images.image_sizes`` stay the real sizes: targets and detections
+        are scaled per image, and the valid ratios come from the mask."""
+        raw = [x["image"].to(self.device) for x in batched_inputs]
+        sizes = [(t.shape[-2], t.shape[-1]) for t in raw]
+        cv = canvas.choose(max(s[0] for s in sizes), max(s[1] for s in sizes), self._canvas_sizes)
+        if cv is None:
+            return None, None
+        if canvas.supported(raw):
+            tensor, mask = canvas.place(raw, cv, self.pixel_mean, self.pixel_std)
+        else:   # CPU tensors, other dtypes / layouts, more than 8 images: the op chain, padded to the canvas
+            tensor, mask = canvas.place_reference(raw, cv, self.pixel_mean, self.pixel_std)
+        samples = NestedTensor(tensor, mask)
+        samples.no_padding = all(tuple(s) == cv for s in sizes)   # known on the host
+        return ImageList(tensor, sizes), samples
 
     def _backbone_tensors(self, images, mask):
         """tensor-in / tensor-out view of the backbone for graph capture."""
@@ -385,8 +424,10 @@ class GroundingDINO(nn.Module):
         side = self._prefetch_stream
         side.wait_stream(cur)          # (the inputs may have been produced on the current stream)
         with torch.cuda.stream(side), torch.no_grad():
-            images = self.preprocess_image(batched_inputs)
-            samples = nested_tensor_from_tensor_list(images)
+            images, samples = self._canvas_batch(batched_inputs) if self._canvas_sizes is not None else (None, None)
+            if samples is None:
+                images = self.preprocess_image(batched_inputs)
+                samples = nested_tensor_from_tensor_list(images)
             captions, names_list = self._captions(batched_inputs)
             overlap, self.overlap_text_and_image = self.overlap_text_and_image, False   # already off the main stream
             try:
@@ -420,8 +461,10 @@ class GroundingDINO(nn.Module):
             # A prefetch that this call does not consume (a handle for another minibatch) may still be running: it
             # replays the SAME front-end graphs, whose static input / output buffers this call is about to use.
             torch.cuda.current_stream(self._prefetch_stream.device).wait_stream(self._prefetch_stream)
-        images = self.preprocess_image(batched_inputs)
-        samples = nested_tensor_from_tensor_list(images)
+        images, samples = self._canvas_batch(batched_inputs) if self._canvas_sizes is not None else (None, None)
+        if samples is None:
+            images = self.preprocess_image(batched_inputs)
+            samples = nested_tensor_from_tensor_list(images)
         captions, names_list = self._captions(batched_inputs)
         finish_text, cate_to_token_mask_list = self.encode_text(captions, samples.device, defer=True)
 
