@@ -236,8 +236,16 @@ int zira_xty_f32(const float *X, const float *Y, int B, int N, int a, int b, int
  * mask_l [B,T] / mask_v [B,N]: bytes, non-zero = padded, may be NULL.  colmax [B,H*T] and gmax [1]
  * are outputs of the forward that the backward needs again.  The backward takes the gradients
  * w.r.t. pv, e and colsum and returns those w.r.t. xm and c; it assumes e and colsum are only
- * used as e / colsum (then the paths through the two maxima vanish).  H*T <= 4096.
- * workspace: zira_bisoftmax_workspace_floats(B, N, H, T) floats, no initialisation needed. */
+ * used as e / colsum (then the paths through the two maxima vanish).  H*T <= 2048 (above that both
+ * entry points return ZIRA_MSDA_EINVAL and launch nothing).  stable / clamp_lo / clamp_hi switch the
+ * global-max shift and the -50000 / +50000 clamps; a clamp passes the gradient where its input lies
+ * within the bounds, bounds included (torch.clamp).  Both maxima run over every entry, padded ones
+ * included; gmax = max(x) is written whatever `stable` is.
+ * Fully padded inputs: an image whose text tokens are all padded has pv = 0 (no NaN, unlike
+ * torch.softmax of all -inf) and gets nothing through g_pv; an image whose image tokens are all padded
+ * has e = 0 and colsum = 0 (the caller's e / colsum is then 0 / 0).
+ * workspace: zira_bisoftmax_workspace_floats(B, N, H, T) floats, no initialisation needed; the same
+ * buffer may serve the forward and the backward.  Deterministic (partial sums folded in a fixed order). */
 size_t zira_bisoftmax_workspace_floats(int B, int N, int H, int T);
 
 int zira_bisoftmax_fwd_f32(const float *xm, const float *c, const uint8_t *mask_l, const uint8_t *mask_v,

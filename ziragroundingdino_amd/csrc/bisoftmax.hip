@@ -6,6 +6,9 @@
 //   p_v[b,n,h,:] = softmax_t(x1 masked to -inf on padded text tokens)
 //   x2 = clamp(x1 - max_n x1)                           per (b,h,t) column
 //   e[b,n,h,t] = exp(x2), 0 on padded image tokens;     colsum[b,h,t] = sum_n e      (p_l = e / colsum)
+// Both maxima run over every entry, padded ones included (as the reference's do).  An image whose text tokens are all
+// padded has p_v = 0 (torch.softmax of all -inf would give NaN; every forward kernel writes 0 for a padded token, whatever
+// the sum is); an image whose image tokens are all padded has e = 0 and colsum = 0.  gmax is written whatever `stable` is.
 //
 // PyTorch runs this as ~300 small kernels per layer and direction (transposes, two full
 // reductions, clamps, masked fills, two softmaxes: 870 us per layer at N = 22223, H*T = 64).  Here
@@ -169,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void bis_rows_fwd(
                 const float ex = (in && on) ? expf(x - m) : 0.f;
                 float sum = ex;
                 for (int d = 1; d < G; d <<= 1) sum += __shfl_xor(sum, d);
-                if (in) tile2[idx] = on ? ex * (1.f / sum) : 0.f;   // all text tokens masked: 0 * inf = nan, as torch.softmax of all -inf
+                if (in) tile2[idx] = on ? ex * (1.f / sum) : 0.f;   // all text tokens masked: sum = 0, but no lane is `on`: p_v = 0, no NaN
             }
         } else
         // ... or one thread's walk for longer texts
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void bis_rows_fwd(
             float s = 0.f;
             for (int k = 0, t = t0; k < T; ++k, t = t + 1 == T ? 0 : t + 1)
                 if (live[t] != 0.f) s += expf(x1[t] - m);
-            const float inv = 1.f / s;  // all text tokens masked: 0 * inf = nan, as torch.softmax of all -inf
+            const float inv = 1.f / s;  // all text tokens masked: inv = inf is never multiplied, every token takes the 0 below: p_v = 0, no NaN
             float *o = tile2 + r * HT + h * T;
             for (int k = 0, t = t0; k < T; ++k, t = t + 1 == T ? 0 : t + 1)
                 o[t] = live[t] != 0.f ? expf(x1[t] - m) * inv : 0.f;
