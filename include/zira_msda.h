@@ -611,9 +611,15 @@ int zira_box_head_bwd_f32(const float *g_out, const float *out, const float *ref
  *     reaches l_ln directly; may be null); W1T [2 H Dv + H, Dl] = W1 transposed; scratch: zira_text_side_scratch_floats floats
  *     (the partial products of the K split; also enough for zira_text_out_fwd_f32).
  * zira_text_out_fwd_f32: out [B, T, Dl] = l_ln + scale (o0 + U O),  U[b t, h Dv + d] = u[b, h T + t, d] / colsum[b, h T + t],
- *     O [H Dv, Dl], scale[b, n] = gamma[n] * keep[b] (keep: the per-sample stochastic-depth factor, may be null).
+ *     O [H Dv, Dl], scale[b, n] = gamma[n] * keep[b] (keep: the per-sample stochastic-depth factor, may be null = 1; an image
+ *     with keep[b] = 0 gets out = l_ln and zero gradients exactly).  An image whose colsum is 0 with u = 0 -- what the
+ *     bi-softmax hands over when every image token of it is masked -- is 0 / 0: out and g_colsum are NaN on all of it and g_u
+ *     is nowhere finite, as in the ATen composition; the other images, also those that share a row tile with it, are not touched
+ *     by that.
  * zira_text_out_bwd_f32: g [B, T, Dl] -> g_u [B, H T, Dv], g_colsum [B, H T]  (the gradient of l_ln is g itself); OT [Dl, H Dv] =
- *     O transposed.  Limit: Dl <= 256 (otherwise hipErrorInvalidValue). */
+ *     O transposed.  Limits: Dl <= 256, every dimension >= 1, B T and H Dv <= 2^20: otherwise hipErrorInvalidValue with nothing
+ *     launched (zira_text_side_scratch_floats returns 0 for such dimensions); the same for a null pointer other than those named
+ *     above. */
 size_t zira_text_side_scratch_floats(int B, int T, int H, int Dv, int Dl);
 int zira_text_prep_fwd_f32(const float *l_in, const float *ln_w, const float *ln_b, float eps, const float *W1, const float *b1,
                            int B, int T, int H, int Dv, int Dl, float *l_ln, float *a, float *c, float *z, float *stats, void *stream);

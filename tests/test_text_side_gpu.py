@@ -10,9 +10,9 @@ from ziragroundingdino_amd import text_side, transformer as zt
 pytestmark = pytest.mark.gpu
 
 
-def _block(drop_path, seed):
+def _block(drop_path, seed, v_dim=256, l_dim=256, embed_dim=1024, num_heads=4):
     torch.manual_seed(seed)
-    blk = zt.BiAttentionBlock(v_dim=256, l_dim=256, embed_dim=1024, num_heads=4, dropout=0.0, drop_path=drop_path).cuda()
+    blk = zt.BiAttentionBlock(v_dim=v_dim, l_dim=l_dim, embed_dim=embed_dim, num_heads=num_heads, dropout=0.0, drop_path=drop_path).cuda()
     for n, p in blk.named_parameters():
         if p.dim() > 1:
             p.data.normal_(0, 0.05)
@@ -26,18 +26,22 @@ def _block(drop_path, seed):
     return blk.train()
 
 
-@pytest.mark.parametrize("case", [(2, 1500, 32, 0.0), (2, 1500, 32, 0.3), (3, 700, 9, 0.0), (1, 400, 195, 0.0)])
+# (B, N, T, drop_path) at the model's widths, and one block at other widths (v_dim, l_dim, embed_dim, heads): Dv = 64, Dl = 128
+# -- one forward K chunk, H Dv = 128: the backward's mixed chunk without columns of a (tests/textside_cases.py)
+@pytest.mark.parametrize("case", [(2, 1500, 32, 0.0), (2, 1500, 32, 0.3), (3, 700, 9, 0.0), (1, 400, 195, 0.0),
+                                  (2, 300, 9, 0.0, (64, 128, 256, 2))])
 def test_native_text_side_matches_the_aten_block(case):
-    B, N, T, dp = case
-    blk = _block(dp, seed=T)
+    B, N, T, dp = case[:4]
+    v_dim, l_dim, embed_dim, heads = case[4] if len(case) > 4 else (256, 256, 1024, 4)
+    blk = _block(dp, T, v_dim, l_dim, embed_dim, heads)
     g = torch.Generator().manual_seed(B * 10 + T)
-    v0 = torch.randn(B, N, 256, generator=g).cuda()
-    l0 = torch.randn(B, T, 256, generator=g).cuda()
+    v0 = torch.randn(B, N, v_dim, generator=g).cuda()
+    l0 = torch.randn(B, T, l_dim, generator=g).cuda()
     mask_v = torch.zeros(B, N, dtype=torch.bool, device="cuda")
     mask_v[-1, N - N // 5:] = True
     mask_l = torch.zeros(B, T, dtype=torch.bool, device="cuda")
     mask_l[0, T - max(1, T // 4):] = True
-    gv, gl = torch.randn(B, N, 256, generator=g).cuda(), torch.randn(B, T, 256, generator=g).cuda()
+    gv, gl = torch.randn(B, N, v_dim, generator=g).cuda(), torch.randn(B, T, l_dim, generator=g).cuda()
     res = {}
     for native in (False, True):
         blk.native_text_side = native

@@ -1,5 +1,6 @@
 // textside.hip -- the TEXT side of an image <-> text fusion block (BiAttentionBlock with frozen, composed projections) as
-// six launches instead of ~41 launch-bound ATen kernels per block (C ABI: zira_text_prep_fwd/bwd_f32, zira_text_out_fwd/bwd_f32).
+// seven launches (prep forward 1; prep backward, out forward and out backward 2 each) instead of ~41 launch-bound ATen kernels
+// per block (C ABI: zira_text_prep_fwd/bwd_f32, zira_text_out_fwd/bwd_f32).
 //
 // Reference: BiMultiHeadAttention / BiAttentionBlock (groundingdino/models/GroundingDINO/fuse_modules.py:99-305).  This
 // package re-brackets the block's products around the B x T <= 512 text tokens (transformer.BiMultiHeadAttention.forward) and,

@@ -1,7 +1,7 @@
 """Host side of csrc/textside.hip: the text side of a fusion block with frozen, composed projections as two autograd nodes --
 ``text_prep`` (LayerNorm of the text tokens and the composed projections, written in the layouts the image side's GEMMs and
 the bi-softmax kernel read) and ``text_out`` (the text output's projection, layer scale, stochastic depth and residual) --
-six launches per block forward + backward instead of ~41 ATen kernels of ~3 us each on the step's critical path
+seven launches per block forward + backward (1 + 2 + 2 + 2) instead of ~41 ATen kernels of ~3 us each on the step's critical path
 (transformer.BiAttentionBlock.forward decides; reference fuse_modules.py:99-305)."""
 import torch
 

@@ -679,7 +679,7 @@ class BiAttentionBlock(nn.Module):
 
     def _forward_native_text(self, v, l, attention_mask_v, attention_mask_l):
         """The fused, re-bracketed block with its text side on csrc/textside.hip: LayerNorm of the text, the composed
-        projections in the layouts the image-side GEMMs read, and the text output with its residual -- 6 launches instead of
+        projections in the layouts the image-side GEMMs read, and the text output with its residual -- 7 launches instead of
         ~41 (same arithmetic up to fp32 summation order; ``v`` is already normalised).  None when it does not apply."""
         from . import text_side
         att = self.attn
