@@ -729,6 +729,37 @@ int zira_place_batch_f32(const zira_place_image *images, int n_images, int Hc, i
 int zira_place_batch_u8(const zira_place_image *images, int n_images, int Hc, int Wc, float mean0, float mean1, float mean2,
                         float std0, float std1, float std2, float *canvas, unsigned char *mask, void *stream);
 
+/* COCO box AP matching on the device as one launch (csrc/apmatch.hip): pycocotools' COCOeval.evaluateImg for iouType "bbox",
+ * useCats = 1, over a whole batch -- per (image, label, area range a, IoU threshold t) the greedy, order-dependent matching of
+ * the label's detections (row order, cut to the first max_det) against the label's ground truth.
+ * Detections as zira_detections_f32 writes them: scores [B, K] fp32 (not read: the rows ARE in non-increasing score order, the
+ * caller's precondition), labels [B, K] i64, xyxy [B, K, 4] fp32, n_keep [B] i32 (the first n_keep[b] entries of a row are
+ * valid; values outside 0..K are clamped).  Ground truth padded to G per image: gt_xywh [B, G, 4] fp64 (COCO's x, y, w, h),
+ * gt_area [B, G] fp64, gt_label [B, G] i64, gt_crowd [B, G] u8, n_gt [B] i32 (clamped to 0..G); with G == 0 the five may be null.
+ * iou_thrs: T (1..16) doubles, area_rng: A (1..4) pairs (lo, hi) of doubles, both in HOST memory, read during the call and handed
+ * to the kernel by value (no upload, no host synchronisation).
+ * The GT list of (b, label, a): the not-ignored GTs in original order, then the ignored ones in original order; a GT is ignored
+ * for range a when it is a crowd or area < lo_a or area > hi_a (both ends inclusive).  IoU in fp64, every operation rounded on its
+ * own (no contraction): dw = (double)fl32(x1 - x0), dh likewise, da = dw dh, ga = gw gh, w = fmin(dx + dw, gx + gw) - fmax(dx, gx),
+ * h likewise, iou = 0 where w <= 0 or h <= 0, else i = w h, u = crowd ? da : da + ga - i, iou = i / u.  Per detection, in order:
+ * best = fmin(thr_t, 1 - 1e-10); scan the list, skipping a matched non-crowd GT, stopping at the first ignored GT once a
+ * not-ignored one is held, skipping iou < best, else best = iou and the GT is held (equal IoU: the LATER one wins).  A held GT
+ * sets the detection's matched bit, hands it its ignore flag and is matched from then on; an unmatched detection is ignored when
+ * da < lo_a or da > hi_a.
+ * Outputs, every element written exactly once: rank [B, K] i32 = the number of earlier valid detections of the image with the
+ * same label, -1 at and behind n_keep[b];  matched / ignored [B, K] u64, bit a T + t, zero behind n_keep[b] and where
+ * rank >= max_det;  gt_ignored [B, G] u8, bit a, zero behind n_gt[b];  gt_of [B, K, A T] i32 (nullable) = the matched GT's
+ * original index or -1.
+ * Served: 1 <= B <= 65535, 1 <= K <= 1024, 0 <= G <= 1024, 1 <= max_det <= K, A T <= 64; anything else returns ZIRA_MSDA_EINVAL
+ * (host arithmetic, nothing launched).  One launch, no global atomics, no allocation, no host synchronisation; the result depends
+ * on the inputs alone.  Return 0, ZIRA_MSDA_EINVAL or a hipError_t; enqueue only, on `stream`; capturable. */
+#define ZIRA_AP_MAX_THRS 16
+#define ZIRA_AP_MAX_AREAS 4
+int zira_ap_match(const float *scores, const int64_t *labels, const float *xyxy, const int32_t *n_keep, int B, int K,
+                  const double *gt_xywh, const double *gt_area, const int64_t *gt_label, const unsigned char *gt_crowd,
+                  const int32_t *n_gt, int G, const double *iou_thrs, int T, const double *area_rng, int A, int max_det,
+                  int32_t *rank, uint64_t *matched, uint64_t *ignored, unsigned char *gt_ignored, int32_t *gt_of, void *stream);
+
 /* Human-readable build tag, e.g. "zira_msda 0.1 gfx950". Static storage. */
 const char *zira_msda_version(void);
 

@@ -36,6 +36,7 @@ SYMBOLS = (
     "zira_topk_rows_workspace_bytes", "zira_topk_rows_f32", "zira_detections_f32",
     "zira_optim_tail_workspace_bytes", "zira_grad_sqnorm_f32", "zira_clip_adamw_f32",
     "zira_place_batch_f32", "zira_place_batch_u8",
+    "zira_ap_match",
     "zira_msda_version", "zira_msda_variant_f32",
 )
 
@@ -63,6 +64,7 @@ class RowGemmArgs(ctypes.Structure):
 
 
 PLACE_MAX_IMAGES = 8
+AP_MAX_THRS, AP_MAX_AREAS = 16, 4      # ZIRA_AP_MAX_THRS / ZIRA_AP_MAX_AREAS of include/zira_msda.h
 
 
 class PlaceImage(ctypes.Structure):
@@ -257,6 +259,9 @@ def load():
     for name in ("zira_place_batch_f32", "zira_place_batch_u8"):
         f = getattr(lib, name)
         f.argtypes, f.restype = [ctypes.POINTER(PlaceImage), i, i, i] + [f32] * 6 + [vp, vp, vp], i
+    dp = ctypes.POINTER(f64)
+    lib.zira_ap_match.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, i, dp, i, dp, i, i, vp, vp, vp, vp, vp, vp]
+    lib.zira_ap_match.restype = i
     lib.zira_msda_version.restype = ctypes.c_char_p
     lib.zira_msda_variant_f32.argtypes = [i]
     lib.zira_msda_variant_f32.restype = ctypes.c_char_p

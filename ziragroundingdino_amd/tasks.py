@@ -133,11 +133,13 @@ def _check_matching(model, process_group=None):
 
 
 def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device="cpu", process_group=None,
-             resume=False, on_step=None) -> str:
-    """``do_train`` for one task; returns the path of its ``model_final.pth``."""
+             resume=False, on_step=None, evaluate=None):
+    """``do_train`` for one task; returns the path of its ``model_final.pth``.  ``evaluate``: a callable
+    ``(model, spec) -> dict`` run on the merged model (``do_test`` after training, train_multidatasets.py:338-364, e.g.
+    ``evaluation.inference_on_dataset`` over the task's test set); the return value is then ``(path, its result)``."""
     final = os.path.join(spec.output_dir, "model_final.pth")
     if resume and os.path.exists(final):
-        return final
+        return final if evaluate is None else (final, evaluate(load_model(build_model, final, device), spec))
     model = load_model(build_model, init_checkpoint, device)
     trainer = ZiraTrainer(model, lr=spec.lr, weight_decay=spec.weight_decay, clip_max_norm=spec.clip_max_norm,
                           clip_norm_type=spec.clip_norm_type, process_group=process_group,
@@ -164,15 +166,17 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
     if _is_main(process_group):
         save_checkpoint(spec.output_dir, "model_final", model, trainer, spec.max_iter)
     _barrier(process_group)               # every rank loads this file at the start of the next task
-    return final
+    return final if evaluate is None else (final, evaluate(model, spec))
 
 
 def run_tasks(specs: Sequence[TaskSpec], build_model, init_checkpoint: Optional[str] = None, device="cpu",
-              process_group=None, resume=False, on_step=None) -> List[str]:
+              process_group=None, resume=False, on_step=None, evaluate=None) -> List:
     """The task loop of ``main`` (:531-560): each task starts from the previous one's
-    ``model_final.pth``.  Returns the list of final checkpoints, one per task."""
+    ``model_final.pth``.  Returns the list of final checkpoints, one per task -- with ``evaluate`` (see ``run_task``)
+    the list of ``(checkpoint, result)`` pairs."""
     finals = []
     for spec in specs:
-        init_checkpoint = run_task(spec, build_model, init_checkpoint, device, process_group, resume, on_step)
-        finals.append(init_checkpoint)
+        done = run_task(spec, build_model, init_checkpoint, device, process_group, resume, on_step, evaluate)
+        init_checkpoint = done if evaluate is None else done[0]
+        finals.append(done)
     return finals
