@@ -1,5 +1,5 @@
 // criterion.hip -- the set-prediction losses of all prediction sets of a step (final layer, auxiliary decoder layers, two-stage
-// encoder output) in four launches forward and two backward (C ABI: zira_stacked_losses_fwd_f32 / _bwd_f32).
+// encoder output) in two launches forward and one backward (C ABI: zira_stacked_losses_fwd_f32 / _bwd_f32).
 //
 // Reference: SetCriterion.loss_labels / loss_boxes (groundingdino/models/GroundingDINO/criterion/criterion.py:104-181) with
 // sigmoid_focal_loss (:31-59) and generalized_box_iou (util/box_ops.py:39-66), once per prediction set; this package's
