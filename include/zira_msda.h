@@ -760,6 +760,42 @@ int zira_ap_match(const float *scores, const int64_t *labels, const float *xyxy,
                   const int32_t *n_gt, int G, const double *iou_thrs, int T, const double *area_rng, int A, int max_det,
                   int32_t *rank, uint64_t *matched, uint64_t *ignored, unsigned char *gt_ignored, int32_t *gt_of, void *stream);
 
+/* Pillow's bilinear Image.resize of uint8 images on the device, bit for bit, for a minibatch of differently sized images
+ * (csrc/resample.hip): what detectron2's ResizeTransform computes on the host for the reference's data mapper.
+ * Per axis with input length `in` and output length `out`, in float64 with every operation rounded on its own:
+ *   scale = in / out, fs = max(scale, 1), support = fs, ksize = ceil(support) 2 + 1, and for output index xx
+ *   center = (xx + 0.5) scale, xmin = max(trunc(center - support + 0.5), 0), xmax = min(trunc(center + support + 0.5), in) - xmin,
+ *   w[x] = 1 - a where a = |(x + xmin - center + 0.5) (1 / fs)| < 1, else 0, divided by their sum in index order,
+ *   tap[x] = trunc(w[x] 2^22 + 0.5);  one pass is clamp((2^21 + sum pixel tap) >> 22, 0, 255) in integers.
+ * The horizontal pass runs first into a uint8 image, the vertical pass reads that; channels are independent.  An axis with
+ * out == in gets the taps (2^22, 0) and comes through unchanged, as Pillow's skipped pass leaves it.
+ * images: n_images (1..ZIRA_RESAMPLE_MAX_IMAGES) descriptors in HOST memory, read during the call and handed to the kernels by
+ * value (no upload, no host synchronisation).  src: uint8, element (c, y, x) at src[c stride_c + y stride_r + x stride_x], c < 3,
+ * strides in bytes and >= 1 -- an HWC image, a CHW tensor and a cropped view of either are all sources; flip != 0 reads column
+ * w - 1 - x in place of x.  dst: contiguous [3, new_h, new_w] uint8, every byte written exactly once, any alignment.
+ * Served: h, w, new_h, new_w in 1..ZIRA_RESAMPLE_MAX_SIDE, h <= 8 new_h and w <= 8 new_w (ksize <= ZIRA_RESAMPLE_MAX_TAPS), any
+ * upscale; anything else returns ZIRA_MSDA_EINVAL (host arithmetic, nothing launched) and the size query returns 0.
+ * Workspace, int32 elements, image after image, for each the horizontal axis (w -> new_w) then the vertical one (h -> new_h):
+ * out pairs (xmin, xmax), then out rows of ksize taps (zero from xmax on).  zira_resample_ws_bytes: its size (pointers are not
+ * looked at).  zira_resample_coeffs: one launch fills it, on the device in fp64 (src / dst are not looked at).  zira_resample_u8:
+ * one launch resamples the batch from a filled workspace; bounds read from the workspace are clamped to the source, so a
+ * workspace that was never filled gives wrong bytes, not a fault.  Bytes moved: sum_i 3 (h_i w_i + new_h_i new_w_i) plus the halo
+ * between the 16 x 64 output tiles and the tables.  Return 0, ZIRA_MSDA_EINVAL or a hipError_t; enqueue only, on `stream`;
+ * capturable. */
+#define ZIRA_RESAMPLE_MAX_IMAGES 8
+#define ZIRA_RESAMPLE_MAX_SIDE 4096
+#define ZIRA_RESAMPLE_MAX_TAPS 17
+typedef struct zira_resample_image {
+    const void *src;
+    void *dst;
+    int64_t stride_c, stride_r, stride_x;
+    int32_t h, w, new_h, new_w;
+    int32_t flip;
+} zira_resample_image;
+size_t zira_resample_ws_bytes(const zira_resample_image *images, int n_images);
+int zira_resample_coeffs(const zira_resample_image *images, int n_images, void *ws, size_t ws_bytes, void *stream);
+int zira_resample_u8(const zira_resample_image *images, int n_images, const void *ws, size_t ws_bytes, void *stream);
+
 /* Human-readable build tag, e.g. "zira_msda 0.1 gfx950". Static storage. */
 const char *zira_msda_version(void);
 

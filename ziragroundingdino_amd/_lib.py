@@ -37,6 +37,7 @@ SYMBOLS = (
     "zira_optim_tail_workspace_bytes", "zira_grad_sqnorm_f32", "zira_clip_adamw_f32",
     "zira_place_batch_f32", "zira_place_batch_u8",
     "zira_ap_match",
+    "zira_resample_ws_bytes", "zira_resample_coeffs", "zira_resample_u8",
     "zira_msda_version", "zira_msda_variant_f32",
 )
 
@@ -71,6 +72,17 @@ class PlaceImage(ctypes.Structure):
     """``zira_place_image`` of include/zira_msda.h, field for field."""
     _fields_ = [("data", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
                 ("stride_c", ctypes.c_int64), ("stride_r", ctypes.c_int64)]
+
+
+RESAMPLE_MAX_IMAGES, RESAMPLE_MAX_SIDE, RESAMPLE_MAX_TAPS = 8, 4096, 17      # ZIRA_RESAMPLE_* of include/zira_msda.h
+
+
+class ResampleImage(ctypes.Structure):
+    """``zira_resample_image`` of include/zira_msda.h, field for field."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
+                ("stride_c", ctypes.c_int64), ("stride_r", ctypes.c_int64), ("stride_x", ctypes.c_int64),
+                ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("new_h", ctypes.c_int32), ("new_w", ctypes.c_int32),
+                ("flip", ctypes.c_int32)]
 
 
 class ExtensionMissingError(ImportError):
@@ -262,6 +274,10 @@ def load():
     dp = ctypes.POINTER(f64)
     lib.zira_ap_match.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, i, dp, i, dp, i, i, vp, vp, vp, vp, vp, vp]
     lib.zira_ap_match.restype = i
+    rp = ctypes.POINTER(ResampleImage)
+    lib.zira_resample_ws_bytes.argtypes, lib.zira_resample_ws_bytes.restype = [rp, i], sz
+    lib.zira_resample_coeffs.argtypes, lib.zira_resample_coeffs.restype = [rp, i, vp, sz, vp], i
+    lib.zira_resample_u8.argtypes, lib.zira_resample_u8.restype = [rp, i, vp, sz, vp], i
     lib.zira_msda_version.restype = ctypes.c_char_p
     lib.zira_msda_variant_f32.argtypes = [i]
     lib.zira_msda_variant_f32.restype = ctypes.c_char_p
