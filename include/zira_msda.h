@@ -667,6 +667,28 @@ int zira_topk_rows_f32(const float *x, int rows, int n, int k, float *out_val, i
 int zira_detections_f32(const float *prob, const float *boxes, int B, int Q, int C, int k, const float *sizes, float *scores,
                         int64_t *labels, float *xyxy, int32_t *n_keep, void *ws, size_t ws_bytes, void *stream);
 
+/* The free-text grounding tail as one launch for a batch (csrc/grounding.hip): the reference's `predict`
+ * (groundingdino/util/inference.py:63-79) -- max(dim), > box_threshold, two boolean-mask indexings, > text_threshold per kept row
+ * -- with fixed-size padded outputs and a count per image, bit-identical to the op chain.
+ * prob [B, Q, T] fp32 (probabilities: the caller applies the sigmoid), boxes [B, Q, 4] fp32 cxcywh.  Per image b, with
+ * s[q] = max_t prob[b, q, t]: query q is kept iff s[q] > box_threshold (strict, fp32; a row that holds a NaN has s = NaN and is
+ * not kept, torch.max's rule).  order = 0: the kept queries in ascending q (the boolean mask's order);  order = 1: by descending s,
+ * equal scores by ascending q (the stable descending order of zira_topk_rows_f32).  Per kept entry, at its position p < n_keep[b]:
+ *   query [B, Q] i32 = q;  score [B, Q] = the bit pattern of s;  box [B, Q, 4] = bit copies of boxes[b, q] (no scaling);
+ *   argmax_token [B, Q] i32 = the FIRST index of the maximum (torch.max(dim));
+ *   token_bits [B, Q, W] u32, W = ceil(T / 32): bit t % 32 of word t / 32 is set iff prob[b, q, t] > text_threshold (strict; false
+ *   for a NaN), bits at t >= T are zero.
+ * n_keep [B] i32 = the count; every output entry at a position >= n_keep[b] is zero, so two runs give byte-identical buffers.
+ * boxes and box 16-byte aligned.  Served: 1 <= B <= 65535, 1 <= Q <= 1024, 1 <= T <= 256, order 0 or 1;
+ * zira_ground_workspace_bytes answers 0 for any other shape (host arithmetic, no GPU needed) and the entry then returns
+ * ZIRA_MSDA_EINVAL, nothing launched.  ws: that many bytes on the device; reserved -- the kernel keeps its state on chip and never
+ * touches it.  One launch of one block per image, no global atomics, no allocation, no host synchronisation; capturable.
+ * Return 0, ZIRA_MSDA_EINVAL or a hipError_t; enqueue only, on `stream`. */
+size_t zira_ground_workspace_bytes(int B, int Q, int T);
+int zira_ground_f32(const float *prob, const float *boxes, int B, int Q, int T, float box_threshold, float text_threshold,
+                    int order, int32_t *query, float *score, float *box, int32_t *argmax_token, uint32_t *token_bits,
+                    int32_t *n_keep, void *ws, size_t ws_bytes, void *stream);
+
 
 /* The training tail on the flat gradient bucket as two launches (csrc/optim_tail.hip): L2 norm, clip, AdamW, gradient clear.
  * The bucket grad [n] fp32 holds the gradients of every trainable tensor back to back (packed: a tensor may start at any offset);

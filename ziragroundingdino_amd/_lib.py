@@ -34,6 +34,7 @@ SYMBOLS = (
     "zira_sine_pos_hw_f32", "zira_box_head_fwd_f32", "zira_box_head_bwd_f32",
     "zira_level_valid_ratios_f32", "zira_encoder_ref_points_f32", "zira_encoder_proposals_f32",
     "zira_topk_rows_workspace_bytes", "zira_topk_rows_f32", "zira_detections_f32",
+    "zira_ground_workspace_bytes", "zira_ground_f32",
     "zira_optim_tail_workspace_bytes", "zira_grad_sqnorm_f32", "zira_clip_adamw_f32",
     "zira_place_batch_f32", "zira_place_batch_u8",
     "zira_ap_match",
@@ -260,6 +261,10 @@ def load():
     lib.zira_topk_rows_f32.restype = i
     lib.zira_detections_f32.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.zira_detections_f32.restype = i
+    lib.zira_ground_workspace_bytes.argtypes = [i, i, i]
+    lib.zira_ground_workspace_bytes.restype = sz
+    lib.zira_ground_f32.argtypes = [vp, vp, i, i, i, f32, f32, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.zira_ground_f32.restype = i
     f64 = ctypes.c_double
     lib.zira_optim_tail_workspace_bytes.argtypes = [ll]
     lib.zira_optim_tail_workspace_bytes.restype = sz

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "launch.h"
+#include "stable_desc.h"
 #include "zira_msda.h"
 
 namespace {
@@ -33,16 +34,7 @@ constexpr int kCopies = 8;               // histogram copies: 64 lanes on one di
                                          // digit of any row) are an 8-way LDS conflict instead of a 64-way one
 constexpr size_t kWorkspace = 256;       // reserved: the kernels keep their state on chip (0 must mean "not served")
 
-// Unsigned order == the sort's order.  Integer tests only: a comparison in a flushing float mode would tie denormals with zero.
-__device__ __forceinline__ uint32_t key_of(float x)
-{
-    const uint32_t u = __float_as_uint(x);
-    const uint32_t mag = u & 0x7FFFFFFFu;
-    if (mag > 0x7F800000u) return 0xFFFFFFFFu;   // NaN: in front of +inf (0xFF800000), all NaNs equal
-    if (mag == 0u) return 0x80000000u;           // -0.0 and +0.0 are one value
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
+// (key_of, the entry format and the sorting network: stable_desc.h)
 template <bool IN_LDS>
 __device__ __forceinline__ uint32_t load_key(const uint32_t *keys, const float *__restrict__ x, int i)
 {
@@ -154,24 +146,7 @@ __device__ __forceinline__ unsigned long long select_sorted(const float *__restr
     __syncthreads();
 
     // ---- bitonic network over P = 2^p >= k entries, descending; thread t owns entry t
-    unsigned long long v = t < P ? s.cand[t] : 0ull;
-#pragma unroll 1
-    for (int kk = 2; kk <= P; kk <<= 1) {
-#pragma unroll 1
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            unsigned long long o;
-            if (j >= 64) {
-                __syncthreads();
-                if (t < P) s.cand[t] = v;
-                __syncthreads();
-                o = t < P ? s.cand[t ^ j] : 0ull;
-            } else {
-                o = __shfl_xor(v, j);
-            }
-            const bool take_max = ((t & j) == 0) == ((t & kk) == 0);
-            v = take_max ? (v > o ? v : o) : (v < o ? v : o);
-        }
-    }
+    const unsigned long long v = bitonic_desc(t < P ? s.cand[t] : 0ull, P, s.cand);
     return t < k ? v : 0ull;
 }
 

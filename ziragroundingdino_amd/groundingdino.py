@@ -441,7 +441,15 @@ class GroundingDINO(nn.Module):
                 "finish_text": finish_text, "cate_list": cate_list, "features": features, "poss": poss, "done": done,
                 "stream": side}
 
-    def forward(self, batched_inputs, frontend=None, **kw):
+    def forward_grounding(self, batched_inputs):
+        """The free-text surface (reference GroundingDINO.forward, what ``predict`` reads): ``{"pred_logits": token logits
+        [B, Q, max_text_len], "pred_boxes": [B, Q, 4]}`` of the last decoder layer -- ``class_embed(hs, text_dict)`` without the
+        fold into category logits, padded with -inf as ``ContrastiveEmbed`` pads.  Eval mode; every input carries its own
+        ``"captions"`` string.  ``grounding.predict`` is the tail on top of it."""
+        assert not self.training, "forward_grounding is an eval-mode path"
+        return self.forward(batched_inputs, grounding=True)
+
+    def forward(self, batched_inputs, frontend=None, grounding=False, **kw):
         if frontend is not None and frontend["inputs"] is batched_inputs:
             cur = torch.cuda.current_stream(frontend["samples"].tensors.device)
             cur.wait_event(frontend["done"])
@@ -456,7 +464,7 @@ class GroundingDINO(nn.Module):
                 targets = self.prepare_targets(gt_instances, cate_to_token_mask_list, names_list)
             text_dict, cate_to_token_mask_list, loss_linear_adapter = frontend["finish_text"]()
             return self._forward_rest(batched_inputs, images, samples, features, poss, text_dict, cate_to_token_mask_list,
-                                      loss_linear_adapter, targets)
+                                      loss_linear_adapter, targets, grounding)
         if self._prefetch_stream is not None:
             # A prefetch that this call does not consume (a handle for another minibatch) may still be running: it
             # replays the SAME front-end graphs, whose static input / output buffers this call is about to use.
@@ -476,14 +484,14 @@ class GroundingDINO(nn.Module):
         features, poss = self.run_backbone(samples)
         text_dict, cate_to_token_mask_list, loss_linear_adapter = finish_text()
         return self._forward_rest(batched_inputs, images, samples, features, poss, text_dict, cate_to_token_mask_list,
-                                  loss_linear_adapter, targets)
+                                  loss_linear_adapter, targets, grounding)
 
     def _forward_rest(self, batched_inputs, images, samples, features, poss, text_dict, cate_to_token_mask_list,
-                      loss_linear_adapter, targets):
+                      loss_linear_adapter, targets, grounding=False):
         out_or_loss = self.forward_features(features, poss, samples.mask, text_dict,
                                             cate_to_token_mask_list, loss_linear_adapter, targets,
-                                            no_padding=getattr(samples, "no_padding", False))
-        if self.training:
+                                            no_padding=getattr(samples, "no_padding", False), token_logits=grounding)
+        if self.training or grounding:
             return out_or_loss
         out = out_or_loss
         return self.postprocess(out["pred_logits"], out["pred_boxes"], batched_inputs, images.image_sizes)
@@ -513,11 +521,13 @@ class GroundingDINO(nn.Module):
         return processed
 
     def forward_features(self, features, poss, samples_mask, text_dict, cate_to_token_mask_list,
-                         loss_linear_adapter=None, targets=None, no_padding=False):
+                         loss_linear_adapter=None, targets=None, no_padding=False, token_logits=False):
         """Everything downstream of the frozen backbone / text encoder: input projections with
         the vision side branches, transformer, heads, and in training mode the criterion
         (reference :483-587).  ``features``: list of NestedTensor, ``poss``: their position
-        encodings, ``samples_mask``: [B,H,W] padding mask of the input images."""
+        encodings, ``samples_mask``: [B,H,W] padding mask of the input images.  ``token_logits`` (eval mode): the last
+        layer's per-token logits and boxes, without the fold into category logits (``forward_grounding``)."""
+        assert not (token_logits and self.training), "token logits are an eval-mode output"
         poss = list(poss)
         srcs, masks, loss_conv_adapter = [], [], None
 
@@ -568,16 +578,20 @@ class GroundingDINO(nn.Module):
             hs_all = torch.stack(list(hs))                                   # [L, B, Q, d]
             ref_all = torch.stack(list(reference[:-1]))
             outputs_coord_list = box_head(self.bbox_embed[0](hs_all), ref_all)
-            cls_in = torch.cat([hs_all, hs_enc[-1][None]]) if with_enc else hs_all
-            cls_all = recover_to_cls_logits(self.class_embed[0](cls_in, text_dict),
-                                            cate_to_token_mask_list, for_fill=-100.0)
-            outputs_class = cls_all[:n_dec]
         else:
             outputs_coord_list = []
             for layer_ref_sig, layer_bbox_embed, layer_hs in zip(reference[:-1], self.bbox_embed, hs):
                 unsig = layer_bbox_embed(layer_hs) + inverse_sigmoid(layer_ref_sig)
                 outputs_coord_list.append(unsig.sigmoid())
             outputs_coord_list = torch.stack(outputs_coord_list)
+        if token_logits:
+            return {"pred_logits": self.class_embed[-1](hs[-1], text_dict), "pred_boxes": outputs_coord_list[-1]}
+        if shared_heads:
+            cls_in = torch.cat([hs_all, hs_enc[-1][None]]) if with_enc else hs_all
+            cls_all = recover_to_cls_logits(self.class_embed[0](cls_in, text_dict),
+                                            cate_to_token_mask_list, for_fill=-100.0)
+            outputs_class = cls_all[:n_dec]
+        else:
             outputs_class = torch.stack([
                 recover_to_cls_logits(layer_cls_embed(layer_hs, text_dict), cate_to_token_mask_list, for_fill=-100.0)
                 for layer_cls_embed, layer_hs in zip(self.class_embed, hs)])
