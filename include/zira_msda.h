@@ -358,13 +358,18 @@ int zira_msda_sampling_bwd_f32(const float *grad_loc, const float *grad_attn, co
                                const int64_t *shapes, long long N, int M, int L, int P, float *grad_proj, int ld, void *stream);
 
 /* ---- Row-block GEMM of the decoder's queries with its prologues and epilogues (csrc/rowgemm.hip) ----------------
- * C[M, N] = epilogue( prologue(A)[M, K] * op(W) ) in float32 on v_mfma_f32_16x16x4_f32 (exact fp32 products), 16 rows per
+ * C[M, N] = epilogue( prologue(A)[M, K] * op(W) ) in float32 on v_mfma_f32_16x16x4_f32 (exact fp32 products), 16 or 32 rows per
  * workgroup: the nn.Linear calls of a decoder layer on its B x 900 query rows (reference transformer_for_adapter.py:
  * 1001-1006 FFN, :1029-1071 attention in / out projections; ms_deform_attn.py:262-288, :338 the MSDA module's) together
  * with the position-code add in front of them and the residual add + LayerNorm behind them, and the same for their input
  * gradients.  All pointers are device pointers; every field not used stays 0 / NULL.
  *   a, lda            A [M, K], row stride lda floats (rows in batch-first order when a_batch_first, see below)
- *   pos, ldpos        optional [M, K]: the block's A is a + pos for output columns < pos_cols (a multiple of 128), a beyond
+ *   pos, ldpos, pos_cols
+ *                     optional [M, K]: the block's A is a + pos for output columns < pos_cols, a beyond.  pos_cols > 0 with
+ *                     pos set; pos_cols >= N means every column.  A workgroup stages one A for all its columns, so a
+ *                     smaller pos_cols is a whole number of the launch's columns per workgroup: 256 with the LayerNorm
+ *                     epilogue (only pos_cols >= N there), 128 otherwise -- a multiple of 128 always holds, since the 64
+ *                     columns of the narrow w_is_nk = 0 launch divide it.  Anything else returns -3.
  *   w, ldw, w_is_nk   w_is_nk = 1: W [N, K] and C = A W^T (forward of nn.Linear with its weight as stored);
  *                     w_is_nk = 0: W [K, N] and C = A W   (the input gradient, again with the weight as stored)
  *   bias              optional [N]

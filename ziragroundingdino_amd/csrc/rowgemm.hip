@@ -8,8 +8,9 @@
 //
 //     C[M, N] = epilogue( prologue(A)[M, K] * op(W) )
 //
-// for a block of 16 rows per workgroup, with
-//   prologue:  A,  A + pos (for the leading `pos_cols` output columns: q = k = tgt + query_pos, v = tgt in one launch),
+// for a block of 16 or 32 rows per workgroup, with
+//   prologue:  A,  A + pos (for the leading `pos_cols` output columns: q = k = tgt + query_pos, v = tgt in one launch; a
+//              block stages one A for all its columns, so `pos_cols` ends on a block's column boundary or covers the row),
 //              or the LayerNorm input gradient of the rows (dy, x, gamma, mean, rstd -> dx, which is also written out:
 //              it is the gradient of the residual connection in front of the LayerNorm);
 //   op(W):     W^T for W [N, K] (nn.Linear forward) or W for W [K, N] (its input gradient with the weight as stored);
@@ -395,6 +396,7 @@ extern "C" int zira_rowgemm_f32(const zira_rowgemm_args *args, void *stream)
     if (ln ? p.n != 256 : p.n % 128 != 0) return -3;
     if ((p.lda | p.ldw | p.ldc) % 4 != 0 || !aligned16(p.a) || !aligned16(p.w) || !aligned16(p.c)) return -3;
     if (p.pos != nullptr && (p.ldpos % 4 != 0 || !aligned16(p.pos) || p.pos_cols % 128 != 0 || p.lnb_x != nullptr)) return -3;
+    if (p.pos != nullptr && p.pos_cols <= 0) return -3;   // (a position code that no column takes: a caller's mistake)
     if (p.res != nullptr && (p.ldres % 4 != 0 || !aligned16(p.res))) return -3;
     if (p.mask != nullptr && !aligned16(p.mask)) return -3;
     if (p.lnb_x != nullptr) {
@@ -412,6 +414,9 @@ extern "C" int zira_rowgemm_f32(const zira_rowgemm_args *args, void *stream)
     const int rows = (p.m + bm - 1) / bm;
     const bool narrow = bm == 32 && !p.w_is_nk && rows * (p.n / 128) < 160;
     const int threads = ln ? 512 : 256;
+    // a block adds the position code to its A or does not: pos_cols is a whole number of blocks' columns, or every column
+    const int block_cols = ln ? 256 : narrow ? 64 : 128;
+    if (p.pos != nullptr && p.pos_cols < p.n && p.pos_cols % block_cols != 0) return -3;
     const dim3 grid(rows, ln ? 1 : p.n / (narrow ? 64 : 128));
     const size_t lds = (size_t)(bm * (p.k + 4) + 256) * sizeof(float);
     hipStream_t st = static_cast<hipStream_t>(stream);
