@@ -787,6 +787,36 @@ int zira_ap_match(const float *scores, const int64_t *labels, const float *xyxy,
                   const int32_t *n_gt, int G, const double *iou_thrs, int T, const double *area_rng, int A, int max_det,
                   int32_t *rank, uint64_t *matched, uint64_t *ignored, unsigned char *gt_ignored, int32_t *gt_of, void *stream);
 
+/* Pascal VOC box AP matching on the device as one launch (csrc/vocmatch.hip): the detection walk of the reference's `voc_eval`
+ * (groundingdino/evaluation/pascal_voc_evaluation.py) for a whole batch, every label and every IoU threshold at once.
+ * Detections in the CALLER's order (the entry orders them itself): scores [B, K] fp32, labels [B, K] i64, xyxy [B, K, 4] fp32 (the
+ * model's 0-based corners), n_keep [B] i32 (the first n_keep[b] entries of a row are valid; values outside 0..K are clamped).
+ * Ground truth padded to G per image: gt_xyxy [B, G, 4] fp64 (VOC's 1-based inclusive corners, as parsed from the annotation),
+ * gt_label [B, G] i64, gt_difficult [B, G] u8, n_gt [B] i32 (clamped to 0..G); with G == 0 the four may be null.
+ * thrs: T (1..ZIRA_VOC_MAX_THRS) doubles in HOST memory, read during the call and handed to the kernel by value.
+ * Quantisation -- what the reference's text file of detections ("%.3f" score, "%.1f" corners after xmin += 1, ymin += 1 in fp32)
+ * holds when it is parsed back; fp64, every operation rounded on its own (no contraction), rint = round to nearest even:
+ *   qs = rint((double)s * 1000.0) / 1000.0
+ *   x0' = rint((double)fl32(x0 + 1.0f) * 10.0) / 10.0, y0' likewise;  x1' = rint((double)x1 * 10.0) / 10.0, y1' likewise.
+ * (The products are exact in fp64 for fp32 inputs, so this is Python's format(np.float32, ".3f" / ".1f") followed by float().)
+ * Matching, per (image b, label c in 0..num_classes-1, threshold t): the valid detections of b with label c in non-increasing qs,
+ * equal qs in row order (a NaN qs behind every number).  Per detection, over the GTs of (b, c) in their original order:
+ *   iw = fmax(fmin(gx1, x1') - fmax(gx0, x0') + 1, 0), ih likewise, inter = iw ih,
+ *   uni = (x1' - x0' + 1)(y1' - y0' + 1) + (gx1 - gx0 + 1)(gy1 - gy0 + 1) - inter, ov = inter / uni;
+ *   ovmax = the maximum, jmax = the FIRST GT that attains it; without a GT of that label ovmax = -inf.
+ * ovmax > thr_t (strict): GT jmax difficult -> neither TP nor FP; not yet taken at t -> TP, and taken at t from then on; taken -> FP.
+ * Otherwise FP.  Precondition: well-formed boxes (x1 >= x0, y1 >= y0, no NaN), on both sides.
+ * Outputs, every element written exactly once: qscore [B, K] fp64 = qs, 0 at and behind n_keep[b];  tp, fp [B, K] u32, bit t, zero
+ * behind n_keep[b] and for a label outside 0..num_classes-1;  gt_of [B, K, T] i32 (nullable) = jmax where TP, else -1.
+ * Served: 1 <= B <= 65535, 1 <= K <= 1024, 0 <= G <= 1024, 1 <= T <= 16, num_classes >= 1; anything else returns ZIRA_MSDA_EINVAL
+ * (host arithmetic, nothing launched).  One launch, no global atomics, no allocation, no host synchronisation; the result depends
+ * on the inputs alone.  Return 0, ZIRA_MSDA_EINVAL or a hipError_t; enqueue only, on `stream`; capturable. */
+#define ZIRA_VOC_MAX_THRS 16
+int zira_voc_match(const float *scores, const int64_t *labels, const float *xyxy, const int32_t *n_keep, int B, int K,
+                   const double *gt_xyxy, const int64_t *gt_label, const unsigned char *gt_difficult, const int32_t *n_gt, int G,
+                   const double *thrs, int T, int num_classes, double *qscore, uint32_t *tp, uint32_t *fp, int32_t *gt_of,
+                   void *stream);
+
 /* Pillow's bilinear Image.resize of uint8 images on the device, bit for bit, for a minibatch of differently sized images
  * (csrc/resample.hip): what detectron2's ResizeTransform computes on the host for the reference's data mapper.
  * Per axis with input length `in` and output length `out`, in float64 with every operation rounded on its own:

@@ -37,7 +37,7 @@ SYMBOLS = (
     "zira_ground_workspace_bytes", "zira_ground_f32",
     "zira_optim_tail_workspace_bytes", "zira_grad_sqnorm_f32", "zira_clip_adamw_f32",
     "zira_place_batch_f32", "zira_place_batch_u8",
-    "zira_ap_match",
+    "zira_ap_match", "zira_voc_match",
     "zira_resample_ws_bytes", "zira_resample_coeffs", "zira_resample_u8",
     "zira_msda_version", "zira_msda_variant_f32",
 )
@@ -67,6 +67,7 @@ class RowGemmArgs(ctypes.Structure):
 
 PLACE_MAX_IMAGES = 8
 AP_MAX_THRS, AP_MAX_AREAS = 16, 4      # ZIRA_AP_MAX_THRS / ZIRA_AP_MAX_AREAS of include/zira_msda.h
+VOC_MAX_THRS = 16                      # ZIRA_VOC_MAX_THRS
 
 
 class PlaceImage(ctypes.Structure):
@@ -279,6 +280,8 @@ def load():
     dp = ctypes.POINTER(f64)
     lib.zira_ap_match.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, i, dp, i, dp, i, i, vp, vp, vp, vp, vp, vp]
     lib.zira_ap_match.restype = i
+    lib.zira_voc_match.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, i, dp, i, i, vp, vp, vp, vp, vp]
+    lib.zira_voc_match.restype = i
     rp = ctypes.POINTER(ResampleImage)
     lib.zira_resample_ws_bytes.argtypes, lib.zira_resample_ws_bytes.restype = [rp, i], sz
     lib.zira_resample_coeffs.argtypes, lib.zira_resample_coeffs.restype = [rp, i, vp, sz, vp], i
