@@ -853,6 +853,42 @@ size_t zira_resample_ws_bytes(const zira_resample_image *images, int n_images);
 int zira_resample_coeffs(const zira_resample_image *images, int n_images, void *ws, size_t ws_bytes, void *stream);
 int zira_resample_u8(const zira_resample_image *images, int n_images, const void *ws, size_t ws_bytes, void *stream);
 
+/* Model exponential moving average on the device (csrc/ema.hip): update, swap and copy as ONE launch each over every fp32
+ * tensor of the model.  The averaged state is one flat fp32 buffer ema [n]; the model's tensors stay the separate tensors they
+ * are and are reached through a device table of segments, ordered by `start`, each inside [0, n) and none overlapping (gaps
+ * between segments are allowed and never touched: the Python side starts every segment on a multiple of 4 elements).  The
+ * flat index space is cut into blocks of ZIRA_EMA_CHUNK elements; block_segment[b] (device, one int32 per block) names the
+ * segment that holds element b * ZIRA_EMA_CHUNK or, where that element lies in a gap, the next one.  A capped grid of
+ * workgroups strides over the blocks.  Indices are 64-bit; n is served from 1 to ZIRA_EMA_MAX_N = 2^31.
+ *
+ * zira_ema_update_f32: per element, fp32, ema = ema * (float)decay + (float)alpha * p -- the product ema * (float)decay is
+ *   rounded on its own (torch._foreach_mul_(ema, decay)), and the rest is
+ *     contracted != 0:  fmaf((float)alpha, p, that product)             (one rounding)
+ *     contracted == 0:  that product + round((float)alpha * p)          (two roundings)
+ *   for torch._foreach_add_(ema, p, alpha=alpha) as the library's kernel was compiled; nothing is left to this compiler.
+ * zira_ema_swap_f32: exchanges every model tensor with its averaged twin.
+ * zira_ema_copy_f32: to_model == 0 copies model -> ema, to_model != 0 copies ema -> model.
+ *
+ * A run of a segment inside a block takes 16-byte accesses only where the ema address and the model address are congruent
+ * modulo 16 (from the first 16-byte boundary on); its ends, and runs whose two addresses differ in phase, go one dword per
+ * lane.  Pointers need 4-byte alignment.  The ema side of every access stays inside the block's own flat range whatever the
+ * table says; the model side is the table's word.  No LDS, no atomics, no workspace, no host synchronisation.  Return 0,
+ * ZIRA_MSDA_EINVAL (n < 1, n > ZIRA_EMA_MAX_N, a null or misaligned pointer, n_segments < 1: nothing is launched) or a
+ * hipError_t; enqueue only, on `stream`; capturable. */
+#define ZIRA_EMA_CHUNK 4096
+#define ZIRA_EMA_MAX_N 2147483648ll
+typedef struct zira_ema_segment {
+    void *param;     /* the model tensor's data (fp32, contiguous) */
+    int64_t start;   /* its first element's index in the flat buffer */
+    int64_t numel;
+} zira_ema_segment;
+int zira_ema_update_f32(float *ema, int64_t n, const zira_ema_segment *segments, int n_segments, const int32_t *block_segment,
+                        double decay, double alpha, int contracted, void *stream);
+int zira_ema_swap_f32(float *ema, int64_t n, const zira_ema_segment *segments, int n_segments, const int32_t *block_segment,
+                      void *stream);
+int zira_ema_copy_f32(float *ema, int64_t n, const zira_ema_segment *segments, int n_segments, const int32_t *block_segment,
+                      int to_model, void *stream);
+
 /* Human-readable build tag, e.g. "zira_msda 0.1 gfx950". Static storage. */
 const char *zira_msda_version(void);
 

@@ -36,6 +36,7 @@ SYMBOLS = (
     "zira_topk_rows_workspace_bytes", "zira_topk_rows_f32", "zira_detections_f32",
     "zira_ground_workspace_bytes", "zira_ground_f32",
     "zira_optim_tail_workspace_bytes", "zira_grad_sqnorm_f32", "zira_clip_adamw_f32",
+    "zira_ema_update_f32", "zira_ema_swap_f32", "zira_ema_copy_f32",
     "zira_place_batch_f32", "zira_place_batch_u8",
     "zira_ap_match", "zira_voc_match",
     "zira_resample_ws_bytes", "zira_resample_coeffs", "zira_resample_u8",
@@ -274,6 +275,9 @@ def load():
     lib.zira_clip_adamw_f32.argtypes = [vp, vp, vp, ll, vp, i, vp, ctypes.POINTER(f64), i, f64, f64, f64, f64, f64, f64, f64, f64, i,
                                         vp, vp, sz, vp]
     lib.zira_clip_adamw_f32.restype = i
+    lib.zira_ema_update_f32.argtypes, lib.zira_ema_update_f32.restype = [vp, ll, vp, i, vp, f64, f64, i, vp], i
+    lib.zira_ema_swap_f32.argtypes, lib.zira_ema_swap_f32.restype = [vp, ll, vp, i, vp, vp], i
+    lib.zira_ema_copy_f32.argtypes, lib.zira_ema_copy_f32.restype = [vp, ll, vp, i, vp, i, vp], i
     for name in ("zira_place_batch_f32", "zira_place_batch_u8"):
         f = getattr(lib, name)
         f.argtypes, f.restype = [ctypes.POINTER(PlaceImage), i, i, i] + [f32] * 6 + [vp, vp, vp], i

@@ -15,8 +15,9 @@ naming the newest -- and the reference's key names, so either side can continue 
 ``model_final.pth`` is written AFTER the merge (the reference's checkpointer hook saves once more from
 ``after_train``), which is what makes the next task start from merged twins and 1e-8 branches.
 
-Only what touches the hot path is here: evaluation, metric writers, EMA and the dataset registry of
-the reference's driver are not.
+Only what touches the hot path is here: evaluation, metric writers and the dataset registry of
+the reference's driver are not.  The model EMA (ema.py) is, off by default:
+``TaskSpec.model_ema`` is the reference's ``train.model_ema``.
 """
 import os
 from dataclasses import dataclass
@@ -25,6 +26,7 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence
 import torch
 import torch.distributed as dist
 
+from . import ema
 from .train import ZiraTrainer
 
 
@@ -54,6 +56,8 @@ class TaskSpec:
     lr_multiplier: Optional[Callable[[int], float]] = None   # default: x0.1 after 40 % (10 epochs, decay at 4)
     checkpoint_period: Optional[int] = None                  # default: max_iter (the configs' 10 epochs)
     batch_size_scale: int = 1                                # optimizer step every k iterations (train_multidatasets.py:192-199)
+    model_ema: Optional[dict] = None                         # train.model_ema: None = off, or dict(decay=0.999, device="")
+    use_ema_weights_for_eval_only: bool = False              # (:338, :534) evaluate a finished task under the averaged weights
 
     def multiplier(self) -> Callable[[int], float]:
         return self.lr_multiplier or multistep_lr_multiplier((self.max_iter * 4) // 10)
@@ -82,9 +86,12 @@ def save_checkpoint(output_dir: str, name: str, model, trainer: ZiraTrainer, ite
     os.makedirs(output_dir, exist_ok=True)
     path = os.path.join(output_dir, name + ".pth")
     tmp = path + ".tmp"
+    # ``may_get_ema_checkpointer`` (:428-429): the checkpointer stores ``ema_state.state_dict()`` beside ``"model"``
+    extra = ema.may_get_ema_checkpointer(model, enabled=getattr(trainer, "model_ema", None) is not None)
+    extra = {k: {n: v.detach().cpu() for n, v in obj.state_dict().items()} for k, obj in extra.items()}
     torch.save({"model": {k: v.detach().cpu() for k, v in model.state_dict().items()},
                 "trainer": {"iteration": iteration, "optimizer": trainer.optimizer.state_dict()},
-                "iteration": iteration}, tmp)
+                "iteration": iteration, **extra}, tmp)
     os.replace(tmp, path)               # a killed run never leaves a half-written file under the final name
     with open(os.path.join(output_dir, "last_checkpoint"), "w") as f:
         f.write(name + ".pth")
@@ -103,6 +110,9 @@ def _resume(spec: TaskSpec, model, trainer: ZiraTrainer) -> int:
     model.load_state_dict(clean_state_dict(checkpoint["model"]), strict=False)
     trainer._bind()
     trainer.optimizer.load_state_dict(checkpoint["trainer"]["optimizer"])
+    for key, obj in ema.may_get_ema_checkpointer(model, enabled=getattr(trainer, "model_ema", None) is not None).items():
+        if key in checkpoint:       # (moved to the device and packed before the first step: ZiraTrainer.ema_before_train)
+            obj.load_state_dict(checkpoint[key])
     return int(checkpoint["trainer"]["iteration"]) + 1
 
 
@@ -136,14 +146,25 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
              resume=False, on_step=None, evaluate=None):
     """``do_train`` for one task; returns the path of its ``model_final.pth``.  ``evaluate``: a callable
     ``(model, spec) -> dict`` run on the merged model (``do_test`` after training, train_multidatasets.py:338-364, e.g.
-    ``evaluation.inference_on_dataset`` over the task's test set); the return value is then ``(path, its result)``."""
+    ``evaluation.inference_on_dataset`` over the task's test set); the return value is then ``(path, its result)``.  With
+    ``spec.model_ema`` it runs a second time under the averaged weights (``apply_model_ema_and_restore``, :356-364) and that
+    result is the first one's ``"ema"`` entry (the reference's ``ret.update(ema_ret)`` overwrites the plain figures instead)."""
     final = os.path.join(spec.output_dir, "model_final.pth")
     if resume and os.path.exists(final):
-        return final if evaluate is None else (final, evaluate(load_model(build_model, final, device), spec))
+        if evaluate is None:
+            return final
+        model = load_model(build_model, final, device)
+        if spec.model_ema is not None:
+            ema.may_build_model_ema(model, enabled=True)
+            checkpoint = torch.load(final, map_location="cpu", weights_only=False)
+            if "ema_state" in checkpoint:
+                model.ema_state.load_state_dict(checkpoint["ema_state"])
+                model.ema_state.to(device)
+        return final, _evaluate(evaluate, model, spec)
     model = load_model(build_model, init_checkpoint, device)
     trainer = ZiraTrainer(model, lr=spec.lr, weight_decay=spec.weight_decay, clip_max_norm=spec.clip_max_norm,
                           clip_norm_type=spec.clip_norm_type, process_group=process_group,
-                          batch_size_scale=spec.batch_size_scale)
+                          batch_size_scale=spec.batch_size_scale, model_ema=spec.model_ema)
     base_lrs = [g["lr"] for g in trainer.optimizer.param_groups]   # before a resume: a checkpoint stores the
     start_iter = _resume(spec, model, trainer) if resume else 0    # MULTIPLIED rates of the iteration it was taken at
     trainer.iter = start_iter             # (the reference's step rule, iter % batch_size_scale == 0, counts from here)
@@ -166,7 +187,22 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
     if _is_main(process_group):
         save_checkpoint(spec.output_dir, "model_final", model, trainer, spec.max_iter)
     _barrier(process_group)               # every rank loads this file at the start of the next task
-    return final if evaluate is None else (final, evaluate(model, spec))
+    return final if evaluate is None else (final, _evaluate(evaluate, model, spec))
+
+
+def _evaluate(evaluate, model, spec: TaskSpec):
+    """``do_test`` (:338-365).  EMA off: ``evaluate(model, spec)`` as it is."""
+    if spec.model_ema is None or not getattr(model, "ema_state", None) or not model.ema_state.has_inited():
+        return evaluate(model, spec)
+    if spec.use_ema_weights_for_eval_only:      # (:534-535) apply without restore, then evaluate
+        ema.apply_model_ema(model)
+        return evaluate(model, spec)
+    result = evaluate(model, spec)
+    with ema.apply_model_ema_and_restore(model):
+        ema_result = evaluate(model, spec)
+    result = dict(result)
+    result["ema"] = ema_result
+    return result
 
 
 def run_tasks(specs: Sequence[TaskSpec], build_model, init_checkpoint: Optional[str] = None, device="cpu",

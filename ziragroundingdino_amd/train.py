@@ -35,8 +35,21 @@ def lr_factor(name: str) -> float:
 class ZiraTrainer:
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), clip_max_norm=0.1,
                  clip_norm_type=2.0, process_group=None, tuned_gemms=True, amp_dtype=None, batch_size_scale=1,
-                 grad_scaler=None):
+                 grad_scaler=None, model_ema=None):
         self.model = model
+        # ``train.model_ema`` of the reference's configs: None = off (nothing below exists then), or
+        # ``dict(decay=0.999, device="")``.  ``may_build_model_ema`` (train_multidatasets.py:408) + ``EMAHook`` (:448): the
+        # state hangs on the model as ``ema_state``, is initialised before the first step and updated after every one.
+        self.model_ema = None if model_ema is None else dict(model_ema)
+        self._ema_updater = None
+        if self.model_ema is not None:
+            from . import ema
+
+            self._ema_model = ema._remove_ddp(model)
+            ema.may_build_model_ema(self._ema_model, enabled=not hasattr(self._ema_model, "ema_state"))
+            device = self.model_ema.get("device") or str(next(model.parameters()).device)   # (EMAHook.__init__: or cfg.model.device)
+            self._ema_updater = ema.EMAUpdater(self._ema_model.ema_state, decay=self.model_ema.get("decay", 0.999), device=device)
+            self._ema_started = False
         # ``train.amp.enabled`` of the reference's configs (Trainer.run_step :170-174 wraps the forward in
         # autocast); here the dtype is named.  bf16 needs no GradScaler; fp16 (the reference's autocast default)
         # gets one, as in Trainer.__init__ :131-136.  The native fp32 ops (MSDA, side branch epilogue,
@@ -151,6 +164,8 @@ class ZiraTrainer:
         and picked up by the next ``run_step(next_data, ...)`` (see GroundingDINO.prefetch_frontend)."""
         assert self.model.training, "[ZiraTrainer] model was changed to eval mode!"
         self._check_bucket()
+        if self._ema_updater is not None and not self._ema_started:
+            self.ema_before_train()
         kw = {}
         pre = self._prefetched
         self._prefetched = None
@@ -219,13 +234,31 @@ class ZiraTrainer:
                     self.optimizer.step()
                 self.flat_grad.zero_()  # keeps the views alive (no set_to_none)
         self.iter += 1
+        if self._ema_updater is not None:
+            # EMAHook.after_step, on EVERY iteration (accumulation ones too).  Its guard ``if not self.model.train: return``
+            # tests a bound method, which is always true, so it never fires there; there is none here.
+            self._ema_updater.update(self._ema_model)
         return {k: v.detach() for k, v in loss_dict.items()}
+
+    def ema_before_train(self):
+        """``EMAHook.before_train``: a loaded state (a resumed checkpoint) moves to the device, otherwise the state starts
+        from the model.  ``run_step`` calls it before the first step."""
+        state = self._ema_updater.state
+        if state.has_inited():
+            state.to(self._ema_updater.device)
+        else:
+            self._ema_updater.init_state(self._ema_model)
+        self._ema_started = True
 
     def after_train(self, class_names: List[str] = ()):
         """End of a task (reference Trainer.after_train :221-237)."""
         self.model.add_cls_prompt(list(class_names))
         self.model.after_train()
         self._bind()  # __rep__ created new `scaling` parameters: train those in the next task
+        if self._ema_updater is not None and self._ema_updater.state.has_inited():
+            # the prompt-pool entries created above have no average yet: they start from the model (the reference's
+            # ``apply_to`` would assert on them in the evaluation that follows)
+            self._ema_updater.state.adopt_missing(self._ema_model)
 
 
 def synthetic_batch(batch_size, height=800, width=1333, n_categories=7, boxes_per_image=5, seed=0,
