@@ -733,6 +733,38 @@ int zira_clip_adamw_f32(float *grad, float *exp_avg, float *exp_avg_sq, int64_t 
                         double beta2, double eps, double weight_decay, double bc1, double bc2, double bc2_sqrt, double max_norm,
                         int do_step, float *norm_out, const void *ws, size_t ws_bytes, void *stream);
 
+/* The same tail under fp16 loss scaling, still two launches and no host read: GradScaler.unscale_, the clip, GradScaler.step
+ * (skip on inf / NaN), GradScaler.update (torch._amp_update_scale_) and the gradient clear.  scale (fp32), growth_tracker and
+ * step (int32; step counts the AdamW steps taken, not the calls) are single values in DEVICE memory, 4-byte aligned.
+ *
+ * zira_optim_tail_amp_workspace_bytes(n): per block one double (partial sum) and one int32 (non-finite flag), and a 16-byte
+ *   snapshot of (scale, step): 8 blocks + 16 + 8 ceil(blocks / 2) bytes; 0 where n is not served.
+ *
+ * zira_grad_sqnorm_amp_f32: inv = (float)(1.0 / (double)*scale);  per element flag |= !isfinite(g) on the raw value, then
+ *   u = inv == 1 ? g : g * inv;  ws partial[b] = sum of (double)u (double)u in the order of zira_grad_sqnorm_f32, ws flag[b];
+ *   block 0 copies *scale and *step into the snapshot.  scale and step are only read.
+ *
+ * zira_clip_adamw_amp_f32 reads scale and step from the snapshot only.  Every workgroup re-adds the partials and ORs the flags:
+ *   total_norm, the clip and *norm_out as in zira_clip_adamw_f32, over u (inf or NaN where the gradients are).
+ *   No flag set: t = step + 1; bc1 = 1 - pow(beta1, t), bc2_sqrt = sqrt(1 - pow(beta2, t)) in double on the device (once per
+ *     workgroup), decay and -lr / bc1 formed from them as zira_clip_adamw_f32's launcher forms them on the host; per element the
+ *     update of zira_clip_adamw_f32 on u * clip;  *step = t.
+ *   A flag set: parameters, moments and *step are not written.
+ *   Either way grad = 0 over the whole bucket and *found_inf_out = 0.0f / 1.0f.
+ *   One thread of the launch then updates the live values as torch._amp_update_scale_ does: a flag set: *scale = (float)(*scale
+ *     backoff_factor), *growth_tracker = 0; else s = *growth_tracker + 1, and where s == growth_interval: *scale = (float)(*scale
+ *     growth_factor) if that is finite, *growth_tracker = 0; else *growth_tracker = s  (the products in double).
+ * EINVAL besides zira_clip_adamw_f32's cases: a null or misaligned scale / growth_tracker / step / found_inf_out,
+ * growth_interval < 1, growth_factor or backoff_factor not positive.  Enqueue only; capturable. */
+size_t zira_optim_tail_amp_workspace_bytes(int64_t n);
+int zira_grad_sqnorm_amp_f32(const float *grad, int64_t n, const float *scale, const int32_t *step, void *ws, size_t ws_bytes,
+                             void *stream);
+int zira_clip_adamw_amp_f32(float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const zira_optim_segment *segments,
+                            int n_segments, const int32_t *block_segment, const double *lrs, int n_groups, double beta1,
+                            double beta2, double eps, double weight_decay, double max_norm, float *scale,
+                            int32_t *growth_tracker, int32_t *step, double growth_factor, double backoff_factor,
+                            int growth_interval, float *norm_out, float *found_inf_out, void *ws, size_t ws_bytes, void *stream);
+
 
 /* A minibatch of differently sized images into one fixed canvas, as one launch (csrc/place.hip): the normalised batch tensor
  * canvas [n_images, 3, Hc, Wc] fp32 -- inside image i's rectangle [0, h_i) x [0, w_i) the value (x - mean[c]) / std[c], zero

@@ -6,7 +6,13 @@ divide, ``clamp``, ``mul_``, fused AdamW per group, ``zero_``) and as the two na
 ``--mode both`` (default): warm-up, then the median of REGIONS event-timed regions of ITERS tails each, one JSON line; every
 tail is preceded by a refill of the bucket (a 18.5 MB device copy, timed alone as ``refill``).  ``--mode torch|native
 --iters N``: N tails of one kind and nothing else, for a ``rocprofv3 --kernel-trace --stats -- python scripts/optim_tail_time.py
---mode ...`` run of its own (the per-kernel times of ``profiles/optim_tail.json``)."""
+--mode ...`` run of its own (the per-kernel times of ``profiles/optim_tail.json``).
+
+``--amp``: the fp16 tail instead (``profiles/optim_tail_amp.json``): the bucket holds gradients times the loss scale, the op
+chain is the one ``run_step`` issues with a ``GradScaler`` -- ``unscale_``, ``vector_norm``, add, divide, ``clamp``, ``mul_``,
+``scaler.step`` (fused AdamW per group), ``scaler.update``, ``zero_`` -- and the native pair is ``NativeOptimTail.step_amp`` on
+a scale and a growth tracker of its own.  Beside the medians, the kernels of one tail of each kind are counted with
+``torch.profiler``."""
 import argparse
 import json
 import os
@@ -27,7 +33,7 @@ REGIONS, ITERS, WARMUP = 7, 100, 20
 
 
 class Setup:
-    def __init__(self):
+    def __init__(self, amp=False):
         g = torch.Generator().manual_seed(0)
         self.params = [torch.nn.Parameter((0.05 * torch.randn(x, generator=g)).cuda()) for x, _ in SEGMENTS]
         n = sum(x for x, _ in SEGMENTS)
@@ -39,8 +45,14 @@ class Setup:
             off += p.numel()
         groups = [{"params": [p for p, (_, gi) in zip(self.params, SEGMENTS) if gi == k], "lr": lr} for k, lr in enumerate(LRS)]
         self.optimizer = torch.optim.AdamW(groups, lr=LRS[0], betas=BETAS, weight_decay=WD, fused=True)
-        self.tail = NativeOptimTail(self.params, self.flat, [gi for _, gi in SEGMENTS], betas=BETAS, eps=1e-8, weight_decay=WD)
+        self.tail = NativeOptimTail(self.params, self.flat, [gi for _, gi in SEGMENTS], betas=BETAS, eps=1e-8, weight_decay=WD,
+                                    amp=amp)
         self.n = n
+        if amp:
+            self.scaler = torch.amp.GradScaler("cuda")      # 65536, x2 every 2000 steps, x0.5 on inf: the reference's
+            self.scaler.scale(torch.zeros((), device="cuda"))
+            self.src.mul_(self.scaler.get_scale())
+            self.scale, self.tracker = self.scaler._scale.clone(), self.scaler._growth_tracker.clone()
 
     def refill(self):
         self.flat.copy_(self.src)
@@ -53,6 +65,37 @@ class Setup:
 
     def native_tail(self):
         self.tail.step(LRS, do_step=True, max_norm=MAX_NORM)
+
+    def torch_amp_tail(self):
+        sc = self.scaler
+        sc.unscale_(self.optimizer)
+        total_norm = torch.linalg.vector_norm(self.flat, 2.0)
+        self.flat.mul_(torch.clamp(MAX_NORM / (total_norm + 1e-6), max=1.0))
+        sc.step(self.optimizer)
+        sc.update()
+        self.flat.zero_()
+
+    def native_amp_tail(self):
+        sc = self.scaler
+        self.tail.step_amp(LRS, self.scale, self.tracker, sc.get_growth_factor(), sc.get_backoff_factor(),
+                           sc.get_growth_interval(), max_norm=MAX_NORM)
+
+
+def launches(fn, refill):
+    """The kernels of one tail (the refill's copy not counted), by name, as torch.profiler sees them."""
+    from torch.profiler import ProfilerActivity, profile
+
+    refill()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    names = [e.name for e in prof.events() if getattr(e, "device_type", None) is not None and "CUDA" in str(e.device_type)
+             and not e.name.lower().startswith(("memcpy", "memset"))]
+    by_name = {}
+    for x in names:
+        by_name[x[:96]] = by_name.get(x[:96], 0) + 1
+    return {"launches": len(names), "kernels": by_name}
 
 
 def timed(fn, refill):
@@ -77,11 +120,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=("both", "torch", "native"), default="both")
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--amp", action="store_true", help="the fp16 tail: GradScaler chain against step_amp")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
-    s = Setup()
+    s = Setup(amp=args.amp)
+    torch_tail, native_tail = (s.torch_amp_tail, s.native_amp_tail) if args.amp else (s.torch_tail, s.native_tail)
     if args.mode != "both":
-        fn = s.torch_tail if args.mode == "torch" else s.native_tail
+        fn = torch_tail if args.mode == "torch" else native_tail
         for _ in range(args.iters):
             s.refill()
             fn()
@@ -91,11 +136,17 @@ def main():
     out = {"device": torch.cuda.get_device_name(0), "values": s.n, "tensors": len(SEGMENTS), "regions": REGIONS,
            "iters_per_region": ITERS,
            "refill": timed(lambda: None, s.refill),
-           "torch_chain_with_refill": timed(s.torch_tail, s.refill),
-           "native_with_refill": timed(s.native_tail, s.refill),
+           "torch_chain_with_refill": timed(torch_tail, s.refill),
+           "native_with_refill": timed(native_tail, s.refill),
            # what the native launches must move: the norm pass reads the bucket; the update reads gradient, parameter and
            # two moments and writes all four
            "native_bytes": {"grad_sqnorm_kernel": 4 * s.n, "clip_adamw_kernel": 32 * s.n}}
+    if args.amp:
+        out["amp"] = True
+        out["torch_chain_launches"] = launches(torch_tail, s.refill)
+        out["native_launches"] = launches(native_tail, s.refill)
+        out["found_inf"] = float(s.tail.found_inf)       # 0: the timed tails were steps, not skips
+        out["steps_taken"] = s.tail.sync_step_count()
     print(json.dumps(out), flush=True)
 
 

@@ -36,6 +36,7 @@ SYMBOLS = (
     "zira_topk_rows_workspace_bytes", "zira_topk_rows_f32", "zira_detections_f32",
     "zira_ground_workspace_bytes", "zira_ground_f32",
     "zira_optim_tail_workspace_bytes", "zira_grad_sqnorm_f32", "zira_clip_adamw_f32",
+    "zira_optim_tail_amp_workspace_bytes", "zira_grad_sqnorm_amp_f32", "zira_clip_adamw_amp_f32",
     "zira_ema_update_f32", "zira_ema_swap_f32", "zira_ema_copy_f32",
     "zira_place_batch_f32", "zira_place_batch_u8",
     "zira_ap_match", "zira_voc_match",
@@ -275,6 +276,11 @@ def load():
     lib.zira_clip_adamw_f32.argtypes = [vp, vp, vp, ll, vp, i, vp, ctypes.POINTER(f64), i, f64, f64, f64, f64, f64, f64, f64, f64, i,
                                         vp, vp, sz, vp]
     lib.zira_clip_adamw_f32.restype = i
+    lib.zira_optim_tail_amp_workspace_bytes.argtypes, lib.zira_optim_tail_amp_workspace_bytes.restype = [ll], sz
+    lib.zira_grad_sqnorm_amp_f32.argtypes, lib.zira_grad_sqnorm_amp_f32.restype = [vp, ll, vp, vp, vp, sz, vp], i
+    lib.zira_clip_adamw_amp_f32.argtypes = [vp, vp, vp, ll, vp, i, vp, ctypes.POINTER(f64), i, f64, f64, f64, f64, f64, vp, vp, vp,
+                                            f64, f64, i, vp, vp, vp, sz, vp]
+    lib.zira_clip_adamw_amp_f32.restype = i
     lib.zira_ema_update_f32.argtypes, lib.zira_ema_update_f32.restype = [vp, ll, vp, i, vp, f64, f64, i, vp], i
     lib.zira_ema_swap_f32.argtypes, lib.zira_ema_swap_f32.restype = [vp, ll, vp, i, vp, vp], i
     lib.zira_ema_copy_f32.argtypes, lib.zira_ema_copy_f32.restype = [vp, ll, vp, i, vp, i, vp], i

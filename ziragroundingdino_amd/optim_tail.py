@@ -7,7 +7,11 @@ The parameters stay the separate tensors they are (state dict, derived buffers a
 move): the kernel reaches them through a small device table of segments -- pointer, start in the bucket, numel,
 learning-rate group -- and a per-block index of the segment each fixed-size block of the flat index space begins in.  The two
 moments are flat fp32 buffers laid out as the bucket.  ``export_to`` / ``import_from`` carry moments and step count to and
-from a ``torch.optim.AdamW``'s ``state``, for checkpoints written through the optimizer and for changing paths mid-run."""
+from a ``torch.optim.AdamW``'s ``state``, for checkpoints written through the optimizer and for changing paths mid-run.
+
+Under fp16 loss scaling (``NativeOptimTail(..., amp=True)``, ``step_amp``) the same two launches also do the ``GradScaler``'s
+part -- ``unscale_``, the skip of a step whose gradients hold an inf or a NaN, ``update`` -- on the scaler's own device tensors:
+every decision is taken on the device, so the step counter lives there too and nothing is read back."""
 import ctypes
 import math
 
@@ -70,9 +74,14 @@ class NativeOptimTail:
 
     ``group_ids[i]`` is the learning-rate group of ``params[i]`` (an index into the ``lrs`` given to ``step``).  ``norm`` is
     a 0-dim fp32 device tensor that every ``step`` overwrites with the bucket's L2 norm before clipping; reading it is the
-    caller's (only) synchronisation."""
+    caller's (only) synchronisation.
 
-    def __init__(self, params, flat_grad, group_ids, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    ``amp=True`` adds what ``step_amp`` needs: the count of AdamW steps taken as a device int32 (a skipped step does not
+    count, and only the device knows which were skipped), the 0-dim fp32 ``found_inf`` slot (0.0 or 1.0, of the latest
+    ``step_amp``) and the larger workspace.  Such a tail steps through ``step_amp`` only; ``step_count`` is then the value of
+    the last ``sync_step_count()``."""
+
+    def __init__(self, params, flat_grad, group_ids, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amp=False):
         params, group_ids = list(params), [int(g) for g in group_ids]
         if not supported(params, flat_grad):
             raise RuntimeError("NativeOptimTail: these parameters / this bucket are not served (see optim_tail.supported)")
@@ -94,6 +103,14 @@ class NativeOptimTail:
             raise RuntimeError("zira_optim_tail_workspace_bytes(%d) = %d: the library cuts the bucket differently" % (n, self._ws_bytes))
         self._ws = torch.zeros(self._ws_bytes // 8, dtype=torch.float64, device=dev)
         self.norm = torch.zeros((), dtype=torch.float32, device=dev)
+        self.amp = bool(amp)
+        if self.amp:
+            self._amp_ws_bytes = int(self._lib.zira_optim_tail_amp_workspace_bytes(n))
+            if self._amp_ws_bytes < self._ws_bytes + 16 + 4 * len(block_segment) or self._amp_ws_bytes % 8:
+                raise RuntimeError("zira_optim_tail_amp_workspace_bytes(%d) = %d" % (n, self._amp_ws_bytes))
+            self._amp_ws = torch.zeros(self._amp_ws_bytes // 8, dtype=torch.float64, device=dev)
+            self._step_dev = torch.zeros((), dtype=torch.int32, device=dev)
+            self.found_inf = torch.zeros((), dtype=torch.float32, device=dev)
 
     def _views(self, flat, i):
         return flat[self.starts[i]:self.starts[i] + self.numels[i]].view_as(self.params[i])
@@ -127,6 +144,45 @@ class NativeOptimTail:
         if do_step:
             self.step_count += 1
 
+    def step_amp(self, lrs, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, max_norm=0.1):
+        """The fp16 tail on the current stream, two launches, no host read: the bucket holds gradients of ``scale`` times
+        the loss.  ``scale`` (0-dim fp32) and ``growth_tracker`` (0-dim int32) are the ``GradScaler``'s device tensors and
+        are updated in place as ``scaler.update()`` would; ``norm`` gets the norm of the unscaled gradients (inf or NaN where
+        they are), ``found_inf`` 0.0 or 1.0.  With an inf or a NaN in the bucket parameters, moments and the step counter
+        stay as they are; the bucket is cleared either way."""
+        if not self.amp:
+            raise RuntimeError("NativeOptimTail.step_amp: built without amp=True")
+        lrs = [float(x) for x in lrs]
+        if len(lrs) < self.n_groups or len(lrs) > MAX_GROUPS:
+            raise ValueError("NativeOptimTail.step_amp: %d learning rates for %d groups" % (len(lrs), self.n_groups))
+        g = self.flat_grad
+        for name, t, dtype in (("scale", scale, torch.float32), ("growth_tracker", growth_tracker, torch.int32)):
+            if not (torch.is_tensor(t) and t.device == g.device and t.dtype == dtype and t.numel() == 1):
+                raise ValueError("NativeOptimTail.step_amp: %s must be one %s value on %s" % (name, dtype, g.device))
+        n, lib = g.numel(), self._lib
+        c_lrs = (ctypes.c_double * len(lrs))(*lrs)
+        with torch.cuda.device(g.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.zira_grad_sqnorm_amp_f32(g.data_ptr(), n, scale.data_ptr(), self._step_dev.data_ptr(),
+                                              self._amp_ws.data_ptr(), self._amp_ws_bytes, stream)
+            if rc != 0:
+                raise RuntimeError("zira_grad_sqnorm_amp_f32 failed: hipError %d" % rc)
+            rc = lib.zira_clip_adamw_amp_f32(g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n,
+                                             self._segments.data_ptr(), len(self.params), self._block_segment.data_ptr(), c_lrs,
+                                             len(lrs), self.betas[0], self.betas[1], self.eps, self.weight_decay, float(max_norm),
+                                             scale.data_ptr(), growth_tracker.data_ptr(), self._step_dev.data_ptr(),
+                                             float(growth_factor), float(backoff_factor), int(growth_interval),
+                                             self.norm.data_ptr(), self.found_inf.data_ptr(), self._amp_ws.data_ptr(),
+                                             self._amp_ws_bytes, stream)
+            if rc != 0:
+                raise RuntimeError("zira_clip_adamw_amp_f32 failed: hipError %d" % rc)
+
+    def sync_step_count(self):
+        """Read the device step counter of an amp tail into ``step_count`` (one host read) and return it."""
+        if self.amp:
+            self.step_count = int(self._step_dev.item())
+        return self.step_count
+
     def _check_same_params(self, optimizer):
         theirs = [p for grp in optimizer.param_groups for p in grp["params"]]
         if len(theirs) != len(self.params) or {id(p) for p in theirs} != {id(p) for p in self.params}:
@@ -134,8 +190,9 @@ class NativeOptimTail:
 
     def export_to(self, optimizer):
         """Write moments and step count into ``optimizer.state`` (a ``torch.optim.AdamW`` over the same parameters), in the
-        form its own first step would have created."""
+        form its own first step would have created.  (An amp tail reads its device step counter first.)"""
         self._check_same_params(optimizer)
+        self.sync_step_count()
         for grp in optimizer.param_groups:
             on_device = bool(grp.get("fused")) or bool(grp.get("capturable"))
             for p in grp["params"]:
@@ -166,3 +223,5 @@ class NativeOptimTail:
         if len(steps) != 1:
             raise ValueError("NativeOptimTail: the optimizer's parameters are at different steps: %s" % sorted(steps))
         self.step_count = steps.pop()
+        if self.amp:
+            self._step_dev.fill_(self.step_count)

@@ -119,14 +119,21 @@ class ZiraTrainer:
                 group_of = {id(p): gi for gi, grp in enumerate(self.optimizer.param_groups) for p in grp["params"]}
                 self._tail = optim_tail.NativeOptimTail(self.params, self.flat_grad, [group_of[id(p)] for p in self.params],
                                                         betas=betas, eps=self.optimizer.defaults["eps"],
-                                                        weight_decay=weight_decay)
+                                                        weight_decay=weight_decay,
+                                                        amp=self.native_amp_tail and self.amp_dtype is torch.float16)
 
     fused_optimizer = True   # class-level switch (tests compare with the multi-tensor implementation)
     # class-level switch: norm + clip + AdamW + gradient clear as two native launches (csrc/optim_tail.hip) instead of the op
     # chain below, where it serves (L2 clip set, no GradScaler: ``unscale_`` and the inf-skip belong to the scaler).  The
     # moments then live in ``_tail``, not in ``optimizer.state``: ``export_tail_state()`` before ``optimizer.state_dict()``.
     native_tail = False
+    # class-level switch, beside ``native_tail``: with fp16 and an enabled GradScaler the tail is the same two launches, which
+    # then also unscale, skip the step on inf / NaN and update the loss scale -- on the scaler's own ``_scale`` and
+    # ``_growth_tracker`` tensors, so ``get_scale()``, ``state_dict()`` and the next ``scale()`` go on as they are.  Off: fp16
+    # keeps the op chain below, whatever ``native_tail`` says.
+    native_amp_tail = False
     last_grad_norm = None    # 0-dim device tensor: the bucket's norm before the clip, of the latest run_step (no host sync)
+    last_found_inf = None    # 0-dim device tensor, with a GradScaler: nonzero where the latest run_step's gradients held an inf / NaN
 
     def export_tail_state(self):
         """Copy the native tail's moments and step count into ``self.optimizer.state`` (checkpoints, leaving the native path)."""
@@ -137,6 +144,30 @@ class ZiraTrainer:
         """Take moments and step count from ``self.optimizer.state`` (a loaded checkpoint, entering the native path)."""
         if self._tail is not None:
             self._tail.import_from(self.optimizer)
+
+    def _scaler_tensors(self, scaler):
+        """The GradScaler's scale and growth tracker where the native amp tail can run on them, else None (the torch path)."""
+        if not (self.native_tail and self.native_amp_tail and self._tail is not None and getattr(self._tail, "amp", False)):
+            return None
+        if scaler is None or not scaler.is_enabled() or self.clip_max_norm is None or self.clip_norm_type != 2:
+            return None
+        scale, tracker = getattr(scaler, "_scale", None), getattr(scaler, "_growth_tracker", None)
+        dev = self.flat_grad.device
+        for t, dtype in ((scale, torch.float32), (tracker, torch.int32)):
+            if not (torch.is_tensor(t) and t.dim() == 0 and t.dtype == dtype and t.device == dev):
+                return None
+        if not all(hasattr(scaler, f) for f in ("get_growth_factor", "get_backoff_factor", "get_growth_interval")):
+            return None
+        return scale, tracker
+
+    def _scaler_found_inf(self, scaler):
+        """The sum of the per-device flags ``unscale_`` left for this optimizer, as a 0-dim tensor on the bucket's device."""
+        dev = self.flat_grad.device
+        state = getattr(scaler, "_per_optimizer_states", {}).get(id(self.optimizer)) or {}
+        flags = [v.reshape(()).to(dev) for v in state.get("found_inf_per_device", {}).values()]
+        if not flags:       # a disabled scaler unscales nothing
+            return torch.zeros((), dtype=torch.float32, device=dev)
+        return flags[0] if len(flags) == 1 else torch.stack(flags).sum()
 
     def _check_bucket(self):
         """The all-reduce, the clipping and the zeroing act on the flat bucket only: a ``.grad`` that no
@@ -212,12 +243,21 @@ class ZiraTrainer:
         if self.on_reduced_grad is not None:
             self.on_reduced_grad(self.flat_grad)
         stepping = self.iter % self.batch_size_scale == 0   # (:190, :196)
+        amp_tensors = self._scaler_tensors(scaler)
         if (self.native_tail and self._tail is not None and self.clip_max_norm is not None and self.clip_norm_type == 2
                 and scaler is None):
             # the same clip every iteration and step every k-th, as two launches; the learning rates are the torch
             # optimizer's of this moment (a scheduler acting on it keeps working)
             self._tail.step([grp["lr"] for grp in self.optimizer.param_groups], do_step=stepping, max_norm=self.clip_max_norm)
             self.last_grad_norm = self._tail.norm
+        elif amp_tensors is not None:
+            # fp16: unscale, norm, clip, AdamW or the skip, the scale update and the clear, as the same two launches on the
+            # scaler's own tensors (they exist since scaler.scale(losses) above); `stepping` is always true here (the assert
+            # in __init__)
+            scale, tracker = amp_tensors
+            self._tail.step_amp([grp["lr"] for grp in self.optimizer.param_groups], scale, tracker, scaler.get_growth_factor(),
+                                scaler.get_backoff_factor(), scaler.get_growth_interval(), max_norm=self.clip_max_norm)
+            self.last_grad_norm, self.last_found_inf = self._tail.norm, self._tail.found_inf
         else:
             if self.clip_max_norm is not None:
                 if scaler is not None:
@@ -229,6 +269,7 @@ class ZiraTrainer:
             if stepping:
                 if scaler is not None:
                     scaler.step(self.optimizer)
+                    self.last_found_inf = self._scaler_found_inf(scaler)   # (update() drops the flags)
                     scaler.update()
                 else:
                     self.optimizer.step()
