@@ -819,6 +819,35 @@ int zira_ap_match(const float *scores, const int64_t *labels, const float *xyxy,
                   const int32_t *n_gt, int G, const double *iou_thrs, int T, const double *area_rng, int A, int max_det,
                   int32_t *rank, uint64_t *matched, uint64_t *ignored, unsigned char *gt_ignored, int32_t *gt_of, void *stream);
 
+/* COCO box AP accumulation on the device as one launch (csrc/apaccum.hip): the second half of pycocotools' COCOeval.accumulate
+ * over what zira_ap_match left -- per (class c, area range a, max-det index mi, IoU threshold t) the precision at R recall
+ * thresholds and the final recall, bit for bit what the host's numpy fp64 gives.
+ * Detections, n of them (0 <= n < 2^31), ALREADY ordered by the caller: class after class, inside a class in non-increasing
+ * score, equal scores in state order.  rank [n] i32, matched / ignored [n] u64 (bit a T + t), as zira_ap_match wrote them; with
+ * n == 0 the three may be null.  seg_off [C + 1] i64 on the device: class c's detections are seg_off[c] .. seg_off[c + 1] - 1
+ * (values are clamped to 0..n and to a non-negative length, so no table makes the kernel read outside the three arrays); what
+ * lies behind seg_off[C] (padding, labels outside 0..C-1) takes part in nothing.  npig [C, A] i32 on the device: the number of
+ * ground-truth boxes of class c that are not ignored for range a.
+ * max_dets: M (1..ZIRA_AP_MAX_DETS) positive ints, rec_thrs: R (1..ZIRA_AP_MAX_RECS) ascending doubles, both in HOST memory,
+ * read during the call and handed to the kernel by value (no upload, no host synchronisation).
+ * Per cell (c, a, mi, t): npig == 0 -> its R precision entries and its recall entry are -1.  Otherwise the class's detections
+ * with 0 <= rank < max_dets[mi] whose ignored bit a T + t is clear are kept, in order; a kept one is a hit when its matched bit
+ * is set.  Per kept element j, tp / fp = the number of hits / misses among the kept ones up to and including j, as doubles;
+ * rc = tp / npig, pr = tp / (tp + fp + 0x1p-52), every operation rounded on its own (no contraction), the divides correctly
+ * rounded.  recall = the last rc, 0 with nothing kept; precision at r = the maximum of pr[j] over the kept j with
+ * rc[j] >= rec_thrs[r], 0 where there is none (rc never decreases, so this is the envelope read at searchsorted-left).
+ * Outputs, every element written exactly once: precision [T, R, C, A, M] fp64, recall [T, C, A, M] fp64.
+ * Served: 1 <= C <= 65535, 1 <= T <= 16, 1 <= A <= 4, A T <= 64, 1 <= M <= 8, 1 <= R <= 256, every max_dets[mi] >= 1; anything
+ * else, or a null pointer, returns ZIRA_MSDA_EINVAL (host arithmetic, nothing launched).  One launch of C A M blocks of T waves,
+ * no global atomics, no workspace, no allocation, no host synchronisation; the result depends on the inputs alone.  Return 0,
+ * ZIRA_MSDA_EINVAL or a hipError_t; enqueue only, on `stream`; capturable. */
+#define ZIRA_AP_MAX_DETS 8
+#define ZIRA_AP_MAX_RECS 256
+#define ZIRA_AP_MAX_CLASSES 65535
+int zira_ap_accumulate(const int32_t *rank, const uint64_t *matched, const uint64_t *ignored, long long n, const int64_t *seg_off,
+                       const int32_t *npig, int C, int T, int A, const int32_t *max_dets, int M, const double *rec_thrs, int R,
+                       double *precision, double *recall, void *stream);
+
 /* Pascal VOC box AP matching on the device as one launch (csrc/vocmatch.hip): the detection walk of the reference's `voc_eval`
  * (groundingdino/evaluation/pascal_voc_evaluation.py) for a whole batch, every label and every IoU threshold at once.
  * Detections in the CALLER's order (the entry orders them itself): scores [B, K] fp32, labels [B, K] i64, xyxy [B, K, 4] fp32 (the

@@ -39,7 +39,7 @@ SYMBOLS = (
     "zira_optim_tail_amp_workspace_bytes", "zira_grad_sqnorm_amp_f32", "zira_clip_adamw_amp_f32",
     "zira_ema_update_f32", "zira_ema_swap_f32", "zira_ema_copy_f32",
     "zira_place_batch_f32", "zira_place_batch_u8",
-    "zira_ap_match", "zira_voc_match",
+    "zira_ap_match", "zira_ap_accumulate", "zira_voc_match",
     "zira_resample_ws_bytes", "zira_resample_coeffs", "zira_resample_u8",
     "zira_msda_version", "zira_msda_variant_f32",
 )
@@ -69,6 +69,7 @@ class RowGemmArgs(ctypes.Structure):
 
 PLACE_MAX_IMAGES = 8
 AP_MAX_THRS, AP_MAX_AREAS = 16, 4      # ZIRA_AP_MAX_THRS / ZIRA_AP_MAX_AREAS of include/zira_msda.h
+AP_MAX_DETS, AP_MAX_RECS, AP_MAX_CLASSES = 8, 256, 65535      # ZIRA_AP_MAX_DETS / _RECS / _CLASSES
 VOC_MAX_THRS = 16                      # ZIRA_VOC_MAX_THRS
 
 
@@ -290,6 +291,8 @@ def load():
     dp = ctypes.POINTER(f64)
     lib.zira_ap_match.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, i, dp, i, dp, i, i, vp, vp, vp, vp, vp, vp]
     lib.zira_ap_match.restype = i
+    lib.zira_ap_accumulate.argtypes = [vp, vp, vp, ll, vp, vp, i, i, i, ctypes.POINTER(ctypes.c_int32), i, dp, i, vp, vp, vp]
+    lib.zira_ap_accumulate.restype = i
     lib.zira_voc_match.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, i, dp, i, i, vp, vp, vp, vp, vp]
     lib.zira_voc_match.restype = i
     rp = ctypes.POINTER(ResampleImage)

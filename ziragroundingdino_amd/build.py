@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libzira_msda.so")
 OBJ_DIR = os.path.join(_HERE, "csrc", "_obj")
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("msda.hip", "msda_cells.hip", "msda_tiles.hip", "msda_cpu.cpp", "rsb.hip", "xty.hip", "xty_bf16x3.hip", "bisoftmax.hip", "layernorm.hip", "groupnorm.hip", "lsap.hip", "catlogits.hip", "winattn.hip", "refpoints.hip", "attn.hip", "sampling.hip", "gemm_drelu.hip", "rowgemm.hip", "gemm_bf16x3.hip", "gemm_f16x2.hip", "gemm_f16x2_panel.hip", "ffn_f16x2.hip", "thin_f16x2.hip", "criterion.hip", "textside.hip", "topk.hip", "grounding.hip", "optim_tail.hip", "ema.hip", "place.hip", "apmatch.hip", "resample.hip", "vocmatch.hip")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("msda.hip", "msda_cells.hip", "msda_tiles.hip", "msda_cpu.cpp", "rsb.hip", "xty.hip", "xty_bf16x3.hip", "bisoftmax.hip", "layernorm.hip", "groupnorm.hip", "lsap.hip", "catlogits.hip", "winattn.hip", "refpoints.hip", "attn.hip", "sampling.hip", "gemm_drelu.hip", "rowgemm.hip", "gemm_bf16x3.hip", "gemm_f16x2.hip", "gemm_f16x2_panel.hip", "ffn_f16x2.hip", "thin_f16x2.hip", "criterion.hip", "textside.hip", "topk.hip", "grounding.hip", "optim_tail.hip", "ema.hip", "place.hip", "apmatch.hip", "resample.hip", "vocmatch.hip", "apaccum.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "zira_msda.h"), os.path.join(_HERE, "csrc", "msda_internal.h"),
            os.path.join(_HERE, "csrc", "msda_fwd_lean.h"), os.path.join(_HERE, "csrc", "split_arith.h"),
            os.path.join(_HERE, "csrc", "lane_sum.h"), os.path.join(_HERE, "csrc", "launch.h"),
@@ -31,6 +31,8 @@ EXTRA_FLAGS = {
     "place.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt"],
     # COCOeval's IoU is numpy / C doubles, every operation rounded on its own: `da + ga - w * h` must not become an FMA
     "apmatch.hip": ["-ffp-contract=off"],
+    # COCOeval's precision is numpy doubles too: `tp + fp + eps` stays an add in front of the divide
+    "apaccum.hip": ["-ffp-contract=off"],
     # voc_eval's overlap is numpy doubles too, and so is the text round trip of the detections that the kernel restates
     "vocmatch.hip": ["-ffp-contract=off"],
     # Pillow's resampling coefficients are C doubles, every operation rounded on its own: `(xx + 0.5) * scale - support` stays two

@@ -6,8 +6,10 @@ The hot part of COCOeval is ``evaluateImg``: per (image, category, area range, I
 of up to 100 detections against the image's ground truth.  ``match`` runs it for a whole batch in one launch where the
 detections already are (csrc/apmatch.hip, the rules stated at ``zira_ap_match`` in include/zira_msda.h); ``match_reference`` is
 the same function in numpy fp64 on any device, for what ``match_supported`` declines, for CPU tensors and for the tests.
-``CocoBoxEvaluator`` keeps the per-batch results on the device and reads them back once, in ``evaluate()``, which is
-pycocotools' ``accumulate`` + ``summarize`` in numpy fp64.  The arithmetic is pycocotools' throughout -- IoU and areas in fp64
+``CocoBoxEvaluator`` keeps the per-batch results on the device until ``evaluate()``, which is pycocotools' ``accumulate`` +
+``summarize``: ``accumulate_device`` fills the precision / recall tables where the state is (csrc/apaccum.hip, one launch, the
+rules stated at ``zira_ap_accumulate``) and only the tables are read back; ``accumulate`` is the same function in numpy fp64 on
+the host -- the same bits -- for what ``accumulate_supported`` declines; ``summarize`` works on the small tables.  The arithmetic is pycocotools' throughout -- IoU and areas in fp64
 from the fp32 xyxy -> xywh conversion the reference's ``instances_to_coco_json`` does; the one deliberate difference from a
 round trip through pycocotools is the input: tensors instead of files.
 
@@ -22,7 +24,8 @@ from . import _lib
 
 MAX_B, MAX_K, MAX_G, MAX_BITS = 65535, 1024, 1024, 64
 MAX_THRS, MAX_AREAS = _lib.AP_MAX_THRS, _lib.AP_MAX_AREAS
-FORCE_REFERENCE = False     # True: CocoBoxEvaluator matches with match_reference wherever it runs (tests, A/B)
+MAX_DETS, MAX_RECS, MAX_CLASSES, MAX_N = _lib.AP_MAX_DETS, _lib.AP_MAX_RECS, _lib.AP_MAX_CLASSES, 2 ** 31 - 1
+FORCE_REFERENCE = False     # True: CocoBoxEvaluator matches with match_reference and accumulates on the host (tests, A/B)
 
 DEFAULT_IOU_THRS = tuple(np.linspace(0.5, 0.95, int(np.round((0.95 - 0.5) / 0.05)) + 1, endpoint=True).tolist())
 DEFAULT_REC_THRS = tuple(np.linspace(0.0, 1.00, int(np.round((1.00 - 0.0) / 0.01)) + 1, endpoint=True).tolist())
@@ -208,6 +211,86 @@ def accumulate(scores, labels, rank, matched, ignored, gt_label, gt_ignored, num
     return precision, recall
 
 
+_STATE = ("scores", "labels", "rank", "matched", "ignored", "gt_label", "gt_ignored")
+_STATE_DTYPES = (torch.float32, torch.int64, torch.int32, torch.int64, torch.int64, torch.int64, torch.uint8)
+
+
+def accumulate_supported(state, num_classes, iou_thrs, area_rngs, max_dets, rec_thrs=DEFAULT_REC_THRS) -> bool:
+    """True where ``accumulate_device`` runs the kernel: ``state`` is a non-empty list of per-batch dicts (what
+    ``CocoBoxEvaluator`` keeps: ``scores`` / ``labels`` / ``rank`` / ``matched`` / ``ignored`` [B, K], ``gt_label`` /
+    ``gt_ignored`` [B, G]) whose tensors all sit on ONE GPU in the evaluator's dtypes, the parameters are inside the entry's
+    limits, ``rec_thrs`` ascends and the library is there."""
+    if not isinstance(state, (list, tuple)) or not state:
+        return False
+    dev, n = None, 0
+    for b in state:
+        if not isinstance(b, dict) or not all(k in b and torch.is_tensor(b[k]) for k in _STATE):
+            return False
+        dev = b["scores"].device if dev is None else dev
+        if not dev.type == "cuda" or not all(b[k].device == dev and b[k].dtype == d for k, d in zip(_STATE, _STATE_DTYPES)):
+            return False
+        if not all(b[k].shape == b["scores"].shape for k in _STATE[:5]) or b["gt_label"].shape != b["gt_ignored"].shape:
+            return False
+        n += b["scores"].numel()
+    T, A, M, R = len(iou_thrs), len(area_rngs), len(max_dets), len(rec_thrs)
+    if not (1 <= int(num_classes) <= MAX_CLASSES and 1 <= T <= MAX_THRS and 1 <= A <= MAX_AREAS and A * T <= MAX_BITS
+            and 1 <= M <= MAX_DETS and 1 <= R <= MAX_RECS and n <= MAX_N):
+        return False
+    if not all(1 <= int(m) < 2 ** 31 for m in max_dets):
+        return False
+    rec = [float(r) for r in rec_thrs]
+    if rec[0] != rec[0] or not all(b >= a for a, b in zip(rec, rec[1:])):
+        return False
+    try:
+        _lib.load()
+    except _lib.ExtensionMissingError:
+        return False
+    return True
+
+
+def _ordered(state, C, A):
+    """The flat state as ``zira_ap_accumulate`` takes it, by torch on the state's device and without a host wait:
+    (rank, matched, ignored) in class-then-score order, seg_off [C + 1] i64, npig [C, A] i32."""
+    cat = lambda k: torch.cat([b[k].reshape(-1) for b in state])
+    scores, labels, rank, gt_label, gt_ignored = cat("scores"), cat("labels"), cat("rank"), cat("gt_label"), cat("gt_ignored")
+    dev = scores.device
+    key = torch.where((rank >= 0) & (labels >= 0) & (labels < C), labels, torch.full_like(labels, C))
+    by_score = torch.sort(scores, descending=True, stable=True)[1]
+    key, by_key = torch.sort(key[by_score], stable=True)
+    order = by_score[by_key]
+    seg_off = torch.searchsorted(key, torch.arange(C + 1, dtype=torch.int64, device=dev)).contiguous()
+    gt_key = torch.where((gt_label >= 0) & (gt_label < C), gt_label, torch.full_like(gt_label, C))
+    clear = ((gt_ignored.to(torch.int32)[:, None] >> torch.arange(A, dtype=torch.int32, device=dev)[None, :]) & 1) == 0
+    npig = torch.zeros((C + 1, A), dtype=torch.int32, device=dev).index_add_(0, gt_key, clear.to(torch.int32))[:C].contiguous()
+    return rank[order].contiguous(), cat("matched")[order].contiguous(), cat("ignored")[order].contiguous(), seg_off, npig
+
+
+def accumulate_device(state, num_classes, iou_thrs, area_rngs, max_dets, rec_thrs=DEFAULT_REC_THRS):
+    """``accumulate`` where the state is: ``zira_ap_accumulate`` on the current stream (one launch; the host never waits).
+    ``state`` as ``accumulate_supported`` describes it.  torch puts the detections in order -- by class, inside a class by
+    descending score, equal scores in state order (two stable sorts); entries with rank < 0 or a label outside [0, C) go behind
+    the last class and take part in nothing -- and counts the not-ignored GTs per (class, area range).
+    -> (precision [T, R, C, A, M], recall [T, C, A, M]), fp64 device tensors, bit for bit what ``accumulate`` returns."""
+    if not accumulate_supported(state, num_classes, iou_thrs, area_rngs, max_dets, rec_thrs):
+        raise RuntimeError("zira_ap_accumulate does not serve this state (see evaluation.accumulate_supported)")
+    C, T, A, M, R = int(num_classes), len(iou_thrs), len(area_rngs), len(max_dets), len(rec_thrs)
+    lib = _lib.load()
+    dev = state[0]["scores"].device
+    with torch.cuda.device(dev):
+        rank, matched, ignored, seg_off, npig = _ordered(state, C, A)
+        n = rank.numel()
+        precision = torch.empty((T, R, C, A, M), dtype=torch.float64, device=dev)
+        recall = torch.empty((T, C, A, M), dtype=torch.float64, device=dev)
+        ptr = lambda t: t.data_ptr() if n > 0 else None
+        rc = lib.zira_ap_accumulate(ptr(rank), ptr(matched), ptr(ignored), n, seg_off.data_ptr(), npig.data_ptr(), C, T, A,
+                                    (ctypes.c_int32 * M)(*[int(m) for m in max_dets]), M,
+                                    (ctypes.c_double * R)(*[float(r) for r in rec_thrs]), R, precision.data_ptr(),
+                                    recall.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        raise RuntimeError("zira_ap_accumulate failed: hipError %d" % rc)
+    return precision, recall
+
+
 def _mean(x):
     x = x[x > -1]
     return float(np.mean(x)) if x.size else -1.0
@@ -231,12 +314,12 @@ def summarize(precision, recall, class_names, iou_thrs, max_dets):
     return out
 
 
-_STATE = ("scores", "labels", "rank", "matched", "ignored", "gt_label", "gt_ignored")
-
-
 class CocoBoxEvaluator:
     """detectron2's ``DatasetEvaluator`` surface (``reset`` / ``process`` / ``evaluate``) for COCO box AP.  ``process`` pads the
-    batch, matches it in one launch and keeps the result where it is; nothing is read back before ``evaluate()``."""
+    batch, matches it in one launch and keeps the result where it is; nothing is read back before ``evaluate()``, which
+    accumulates where the state is (``accumulate_device``) and reads back the two tables, or -- CPU state, state on several
+    devices after ``merge``, parameters outside the entry's limits, ``FORCE_REFERENCE`` -- reads back the state and accumulates
+    on the host.  The tables are the same bits either way."""
 
     def __init__(self, class_names, max_dets=(1, 10, 100), iou_thrs=None, area_rngs=None):
         self.class_names = list(class_names)
@@ -321,6 +404,13 @@ class CocoBoxEvaluator:
         return host
 
     def evaluate(self):
+        C = len(self.class_names)
+        if not FORCE_REFERENCE and accumulate_supported(self._batches, C, self.iou_thrs, self.area_rngs, self.max_dets):
+            p, r = accumulate_device(self._batches, C, self.iou_thrs, self.area_rngs, self.max_dets)
+            both = torch.cat([p.view(-1), r.view(-1)]).cpu().numpy()      # ONE device -> host copy
+            precision, recall = both[:p.numel()].reshape(tuple(p.shape)), both[p.numel():].reshape(tuple(r.shape))
+            self.precision, self.recall = precision, recall
+            return {"bbox": summarize(precision, recall, self.class_names, self.iou_thrs, self.max_dets)}
         host = self._gather()
         cat = lambda k, dt: np.concatenate([h[k] for h in host]) if host else np.zeros(0, dt)
         rank, gt_label = cat("rank", np.int32), cat("gt_label", np.int64)
