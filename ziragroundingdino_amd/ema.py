@@ -27,9 +27,10 @@ from .transformer import Switches
 
 logger = logging.getLogger(__name__)
 
-CHUNK = 4096        # ZIRA_EMA_CHUNK: elements of the flat index space per block
+CHUNK = _lib.CONSTANTS["ZIRA_EMA_CHUNK"]        # elements of the flat index space per block
 ALIGN = 4           # every segment starts on a multiple of 4 elements: 16 bytes, the phase of a tensor from the allocator
-MAX_N = 1 << 31     # ZIRA_EMA_MAX_N
+MAX_N = _lib.CONSTANTS["ZIRA_EMA_MAX_N"]
+_lib.assert_int64_rows(_lib.EmaSegment, ("param", "start", "numel"))      # the rows _table_for uploads
 # ``torch._foreach_add_(ema, p, alpha=a)`` computes ``ema + a * p``: True where the library's kernel holds that as one fused
 # multiply-add, False where it rounds the product first.  tests/test_ema_gpu.py decides it (bit equality with the chain on
 # the same device).  Found on an MI355X: contracted (the other form differs in a tenth of the elements); DESIGN.md.

@@ -19,9 +19,10 @@ import torch
 
 from . import _lib
 
-CHUNK = 4096        # ZIRA_OPTIM_TAIL_CHUNK: elements of the flat index space per workgroup
-MAX_GROUPS = 8      # ZIRA_OPTIM_TAIL_MAX_GROUPS
+CHUNK = _lib.CONSTANTS["ZIRA_OPTIM_TAIL_CHUNK"]        # elements of the flat index space per workgroup
+MAX_GROUPS = _lib.CONSTANTS["ZIRA_OPTIM_TAIL_MAX_GROUPS"]
 MAX_N = 1 << 26
+_lib.assert_int64_rows(_lib.OptimSegment, ("param", "start", "numel", "group"))      # the rows NativeOptimTail uploads
 
 
 def plan_segments(numels, group_ids, chunk=CHUNK):
