@@ -1,7 +1,7 @@
-"""Reader of include/zira_msda.h: the header's prototypes, structs and limits as ctypes objects.
+"""Reader of include/zira_msda.h and include/zira_metrics.h: a header's prototypes, structs and limits as ctypes objects.
 
-Not a C parser.  The header keeps to ``ret zira_name(type name, ...);``, ``typedef struct zira_x { type a, b; ... } zira_x;``
-and ``#define ZIRA_NAME <integer>``; anything else raises ``HeaderError`` with the line it stands on -- nothing is guessed and
+Not a C parser.  The headers keep to ``ret zira_name(type name, ...);``, ``typedef struct zira_x { type a, b; type c[N]; ... }
+zira_x;`` and ``#define ZIRA_NAME <integer>``; anything else raises ``HeaderError`` with the line it stands on -- nothing is guessed and
 nothing is skipped.  Where a new declaration does not read, respell the declaration."""
 import ctypes
 import re
@@ -17,6 +17,7 @@ _INTEGER = re.compile(r"(0[xX][0-9a-fA-F]+|[1-9][0-9]*|0)[uUlL]*")
 _NOT_C = re.compile(r'^[ \t]*(#.*|extern[ \t]+"C"[ \t]*\{|\})[ \t]*$', re.M)     # preprocessor lines, the extern "C" bracket
 _STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", re.S)
 _VARIABLE = re.compile(r"(?:const\s+)?(\w+(?:\s+\w+)*?)\s*(\*?)\s*(\w+(?:\s*,\s*\w+)*)")    # [const] type [*] name[, name ...]
+_ARRAY = re.compile(r"(.+?)\s*\[\s*(\w+)\s*\]", re.S)                                      # declaration [N]
 _FUNCTION = re.compile(r"(.+?)\s*\b(zira_\w+)\s*\((.*)\)", re.S)
 
 
@@ -24,7 +25,7 @@ class HeaderError(ImportError):
     pass
 
 
-def parse(text, device_tables=()):
+def parse(text, device_tables=(), name="zira_msda.h"):
     """``(prototypes, structs, constants)`` of the header ``text``: name -> (restype, argtypes), name -> ctypes.Structure
     subclass, name -> int, each in header order.  A scalar is its ctypes scalar, a pointer to a scalar or to void is
     ``c_void_p`` (callers pass addresses, None and ctypes arrays), a pointer to a struct is ``POINTER`` of its class -- except
@@ -34,10 +35,18 @@ def parse(text, device_tables=()):
     prototypes, structs, constants = {}, {}, {}
 
     def fail(pos, what, chunk):
-        raise HeaderError("zira_msda.h line %d: %s: %r" % (text.count("\n", 0, pos) + 1, what, " ".join(chunk.split())))
+        raise HeaderError("%s line %d: %s: %r" % (name, text.count("\n", 0, pos) + 1, what, " ".join(chunk.split())))
 
-    def variable(pos, decl):
-        """``decl`` as (names, ctypes type)."""
+    def variable(pos, decl, member=False):
+        """``decl`` as (names, ctypes type).  A struct member may be one array, ``type name[N]``, N an integer or a limit
+        defined above it."""
+        a = _ARRAY.fullmatch(decl.strip()) if member else None
+        if a:
+            count = constants.get(a.group(2), int(a.group(2)) if a.group(2).isdigit() else 0)
+            names, ctype = variable(pos, a.group(1))
+            if len(names) != 1 or count < 1:
+                fail(pos, "no ctypes mapping for", decl)
+            return names, ctype * count
         m = _VARIABLE.fullmatch(decl.strip())
         base, star, names = (" ".join(m.group(1).split()), m.group(2), m.group(3).replace(",", " ").split()) if m else ("", "", [])
         if not star and base in SCALARS:
@@ -62,7 +71,7 @@ def parse(text, device_tables=()):
         fields = []
         for member in re.finditer(r"[^;]+", m.group(2)):
             if member.group().strip():
-                names, ctype = variable(m.start(2) + member.end() - len(member.group().lstrip()), member.group())
+                names, ctype = variable(m.start(2) + member.end() - len(member.group().lstrip()), member.group(), member=True)
                 fields += [(name, ctype) for name in names]
         structs[m.group(1)] = type(m.group(1), (ctypes.Structure,), {"_fields_": fields})
         return blank(m)

@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI declared in include/zira_msda.h, derived from that header at import (_header.py).
+"""ctypes binding of the C ABI declared in include/zira_msda.h and include/zira_metrics.h, derived from the headers at import
+(_header.py).
 
 There is deliberately no fallback: if ``libzira_msda.so`` is missing the import of the op
 raises, so a GPU box can never silently run a non-HIP path.
@@ -15,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZIRA_MSDA_LIB") or os.path.join(_HERE, "libzira_msda.so")  # env: dev A/B builds
 
 _HEADER = os.path.join(_HERE, os.pardir, "include", "zira_msda.h")
+_METRICS_HEADER = os.path.join(_HERE, os.pardir, "include", "zira_metrics.h")
 # Structs whose arrays are rows of a device tensor (optim_tail.py, ema.py): callers pass ``data_ptr()``, a plain address, which
 # ``POINTER(struct)`` refuses, so their pointers are ``c_void_p``.  The others are host descriptors built with ctypes.
 DEVICE_TABLES = ("zira_optim_segment", "zira_ema_segment")
@@ -23,7 +25,7 @@ DEVICE_TABLES = ("zira_optim_segment", "zira_ema_segment")
 def read_header(path):
     try:
         with open(path) as f:
-            return _header.parse(f.read(), DEVICE_TABLES)
+            return _header.parse(f.read(), DEVICE_TABLES, os.path.basename(path))
     except OSError as e:
         raise _header.HeaderError("cannot read %s (%s): the binding is derived from it" % (path, e)) from e
 
@@ -37,6 +39,10 @@ AP_MAX_THRS, AP_MAX_AREAS = CONSTANTS["ZIRA_AP_MAX_THRS"], CONSTANTS["ZIRA_AP_MA
 AP_MAX_DETS, AP_MAX_RECS, AP_MAX_CLASSES = CONSTANTS["ZIRA_AP_MAX_DETS"], CONSTANTS["ZIRA_AP_MAX_RECS"], CONSTANTS["ZIRA_AP_MAX_CLASSES"]
 RESAMPLE_MAX_IMAGES, RESAMPLE_MAX_SIDE = CONSTANTS["ZIRA_RESAMPLE_MAX_IMAGES"], CONSTANTS["ZIRA_RESAMPLE_MAX_SIDE"]
 RESAMPLE_MAX_TAPS = CONSTANTS["ZIRA_RESAMPLE_MAX_TAPS"]
+# The second public header, the metrics log's (metrics.py), in tables of its own: the ones above are zira_msda.h's alone.
+METRICS_PROTOTYPES, METRICS_STRUCTS, METRICS_CONSTANTS = read_header(_METRICS_HEADER)
+METRICS_SYMBOLS = tuple(METRICS_PROTOTYPES)
+MetricsSources = METRICS_STRUCTS["zira_metrics_sources"]
 
 _lib = None
 
@@ -61,7 +67,7 @@ def load():
             "HIP extension %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or python -m ziragroundingdino_amd.build). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(METRICS_PROTOTYPES.items()):
         f = getattr(lib, name)
         f.argtypes, f.restype = argtypes, restype
     _lib = lib

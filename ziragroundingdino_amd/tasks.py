@@ -15,9 +15,10 @@ naming the newest -- and the reference's key names, so either side can continue 
 ``model_final.pth`` is written AFTER the merge (the reference's checkpointer hook saves once more from
 ``after_train``), which is what makes the next task start from merged twins and 1e-8 branches.
 
-Only what touches the hot path is here: evaluation, metric writers and the dataset registry of
+Only what touches the hot path is here: evaluation and the dataset registry of
 the reference's driver are not.  The model EMA (ema.py) is, off by default:
-``TaskSpec.model_ema`` is the reference's ``train.model_ema``.
+``TaskSpec.model_ema`` is the reference's ``train.model_ema``.  So are the metric writers (metrics.py), off by
+default: ``TaskSpec.log_period`` is the reference's ``train.log_period`` and writes ``<output_dir>/metrics.json``.
 """
 import os
 from dataclasses import dataclass
@@ -58,6 +59,7 @@ class TaskSpec:
     batch_size_scale: int = 1                                # optimizer step every k iterations (train_multidatasets.py:192-199)
     model_ema: Optional[dict] = None                         # train.model_ema: None = off, or dict(decay=0.999, device="")
     use_ema_weights_for_eval_only: bool = False              # (:338, :534) evaluate a finished task under the averaged weights
+    log_period: Optional[int] = None                         # train.log_period (20): <output_dir>/metrics.json every so many iterations; None = off
 
     def multiplier(self) -> Callable[[int], float]:
         return self.lr_multiplier or multistep_lr_multiplier((self.max_iter * 4) // 10)
@@ -162,9 +164,15 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
                 model.ema_state.to(device)
         return final, _evaluate(evaluate, model, spec)
     model = load_model(build_model, init_checkpoint, device)
+    writers = []
+    if spec.log_period is not None and _is_main(process_group):      # (:436-459: the writers are the main process's)
+        from . import metrics
+
+        writers = [metrics.CommonMetricPrinter(spec.max_iter), metrics.JSONWriter(os.path.join(spec.output_dir, "metrics.json"))]
     trainer = ZiraTrainer(model, lr=spec.lr, weight_decay=spec.weight_decay, clip_max_norm=spec.clip_max_norm,
                           clip_norm_type=spec.clip_norm_type, process_group=process_group,
-                          batch_size_scale=spec.batch_size_scale, model_ema=spec.model_ema)
+                          batch_size_scale=spec.batch_size_scale, model_ema=spec.model_ema,
+                          metrics=None if spec.log_period is None else dict(period=spec.log_period, writers=writers))
     base_lrs = [g["lr"] for g in trainer.optimizer.param_groups]   # before a resume: a checkpoint stores the
     start_iter = _resume(spec, model, trainer) if resume else 0    # MULTIPLIED rates of the iteration it was taken at
     trainer.iter = start_iter             # (the reference's step rule, iter % batch_size_scale == 0, counts from here)
@@ -182,6 +190,8 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
             _check_matching(model, process_group)        # before anything is written: one host sync per checkpoint period
             if _is_main(process_group):
                 save_checkpoint(spec.output_dir, "model_%07d" % it, model, trainer, it)
+    for writer in writers:
+        writer.close()
     _check_matching(model, process_group)                # ... and before the side branches are merged into the weights
     trainer.after_train(list(spec.categories_names))
     if _is_main(process_group):

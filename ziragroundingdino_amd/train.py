@@ -35,8 +35,16 @@ def lr_factor(name: str) -> float:
 class ZiraTrainer:
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), clip_max_norm=0.1,
                  clip_norm_type=2.0, process_group=None, tuned_gemms=True, amp_dtype=None, batch_size_scale=1,
-                 grad_scaler=None, model_ema=None):
+                 grad_scaler=None, model_ema=None, metrics=None):
         self.model = model
+        # The reference's ``_write_metrics`` + ``PeriodicWriter`` hooks (train_multidatasets.py:200, :436-459): None = off
+        # (nothing below exists then and run_step is as it was), or ``dict(period=20, window=20, rows=None, writers=[...])``.
+        # Every run_step records its scalars into a device-side log with one launch (metrics.py); every ``period`` iterations
+        # the window is reduced, read once, kept as ``last_metrics`` and handed to the writers.
+        self.metrics = None if metrics is None else dict(metrics)
+        self._metrics_log = None      # built by the first run_step, from the keys of its loss dict
+        self.last_metrics = None
+        self.data_time = 0.0          # the caller's wait for this minibatch, in seconds, set before run_step (a logged column)
         # ``train.model_ema`` of the reference's configs: None = off (nothing below exists then), or
         # ``dict(decay=0.999, device="")``.  ``may_build_model_ema`` (train_multidatasets.py:408) + ``EMAHook`` (:448): the
         # state hangs on the model as ``ema_state``, is initialised before the first step and updated after every one.
@@ -279,7 +287,32 @@ class ZiraTrainer:
             # EMAHook.after_step, on EVERY iteration (accumulation ones too).  Its guard ``if not self.model.train: return``
             # tests a bound method, which is always true, so it never fires there; there is none here.
             self._ema_updater.update(self._ema_model)
+        if self.metrics is not None:
+            self._write_metrics(loss_dict, scaler)
         return {k: v.detach() for k, v in loss_dict.items()}
+
+    def _write_metrics(self, loss_dict, scaler):
+        """``_write_metrics`` on EVERY iteration (accumulation ones too), without the reference's host reads: the losses, the
+        gradient norm, the found-inf flag and the loss scale by pointer, ``lr`` (the largest parameter group's) and
+        ``data_time`` by value.  ``self.iter`` is already the next iteration's number, so ``iter % period == 0`` is the
+        reference's ``(iter + 1) % period == 0``."""
+        from . import metrics as _metrics
+
+        extras = [("grad_norm", self.last_grad_norm), ("found_inf", self.last_found_inf),
+                  ("loss_scale", getattr(scaler, "_scale", None) if scaler is not None else None)]
+        extras = [(k, v) for k, v in extras if torch.is_tensor(v) and v.numel() == 1]
+        names = list(loss_dict) + [k for k, _ in extras] + ["lr", "data_time"]
+        if self._metrics_log is None or self._metrics_log.names != names:
+            window = int(self.metrics.get("window", 20))
+            self._metrics_log = _metrics.DeviceMetrics(names, n_loss=len(loss_dict), window=window, n_host=2,
+                                                       rows=self.metrics.get("rows") or max(window, int(self.metrics.get("period", 20))),
+                                                       device=self.flat_grad.device)
+        lr = max(self.optimizer.param_groups, key=lambda g: len(g["params"]))["lr"]
+        self._metrics_log.record(list(loss_dict.values()) + [v for _, v in extras], [lr, self.data_time])
+        if self.iter % int(self.metrics.get("period", 20)) == 0:
+            self.last_metrics = self._metrics_log.flush(self.group, iteration=self.iter - 1)
+            for writer in self.metrics.get("writers", ()):
+                writer.write(self.last_metrics)
 
     def ema_before_train(self):
         """``EMAHook.before_train``: a loaded state (a resumed checkpoint) moves to the device, otherwise the state starts
