@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI declared in include/zira_msda.h, include/zira_metrics.h and include/zira_rsb_ml.h, derived from
-the headers at import (_header.py).
+"""ctypes binding of the C ABI declared in include/zira_msda.h, include/zira_metrics.h, include/zira_rsb_ml.h and
+include/zira_nms.h, derived from the headers at import (_header.py).
 
 There is deliberately no fallback: if ``libzira_msda.so`` is missing the import of the op
 raises, so a GPU box can never silently run a non-HIP path.
@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("ZIRA_MSDA_LIB") or os.path.join(_HERE, "libzira_msda.
 _HEADER = os.path.join(_HERE, os.pardir, "include", "zira_msda.h")
 _METRICS_HEADER = os.path.join(_HERE, os.pardir, "include", "zira_metrics.h")
 _RSB_ML_HEADER = os.path.join(_HERE, os.pardir, "include", "zira_rsb_ml.h")
+_NMS_HEADER = os.path.join(_HERE, os.pardir, "include", "zira_nms.h")
 # Structs whose arrays are rows of a device tensor (optim_tail.py, ema.py): callers pass ``data_ptr()``, a plain address, which
 # ``POINTER(struct)`` refuses, so their pointers are ``c_void_p``.  The others are host descriptors built with ctypes.
 DEVICE_TABLES = ("zira_optim_segment", "zira_ema_segment")
@@ -47,6 +48,10 @@ MetricsSources = METRICS_STRUCTS["zira_metrics_sources"]
 # The third, the multilayer-branch epilogue's (rsb_multilayer.py): prototypes only.
 RSB_ML_PROTOTYPES = read_header(_RSB_ML_HEADER)[0]
 RSB_ML_SYMBOLS = tuple(RSB_ML_PROTOTYPES)
+# The fourth, the batched box NMS's (nms.py): prototypes and its two limits.
+NMS_PROTOTYPES, _, NMS_CONSTANTS = read_header(_NMS_HEADER)
+NMS_SYMBOLS = tuple(NMS_PROTOTYPES)
+NMS_MAX_K, NMS_MAX_B = NMS_CONSTANTS["ZIRA_NMS_MAX_K"], NMS_CONSTANTS["ZIRA_NMS_MAX_B"]
 
 _lib = None
 
@@ -71,7 +76,8 @@ def load():
             "HIP extension %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or python -m ziragroundingdino_amd.build). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(METRICS_PROTOTYPES.items()) + list(RSB_ML_PROTOTYPES.items()):
+    for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(METRICS_PROTOTYPES.items()) + list(RSB_ML_PROTOTYPES.items())
+                                      + list(NMS_PROTOTYPES.items())):
         f = getattr(lib, name)
         f.argtypes, f.restype = argtypes, restype
     _lib = lib

@@ -172,11 +172,24 @@ def phrases_from_bits(token_bits_row, tokenized, caption: str) -> str:
     return " ".join(pieces).replace(".", "")
 
 
-def predict(model, batched_inputs, box_threshold, text_threshold, order=0):
+def phrase_labels(token_bits):
+    """token_bits [B, Q, W] -> [B, Q] int64: the first row of the image with the same mask words.  Rows of one label decode
+    to one phrase."""
+    same = (token_bits[:, :, None, :] == token_bits[:, None, :, :]).all(dim=-1)
+    return same.to(torch.uint8).argmax(dim=-1)
+
+
+def predict(model, batched_inputs, box_threshold, text_threshold, order=0, nms_threshold=None, nms_per_phrase=False):
     """The reference's ``predict`` for a batch: every input carries its image and its own ``"captions"`` string.  Per image
     ``(boxes [n, 4] cxcywh in 0..1, logits [n], phrases)`` on the host.  The model runs in eval mode without gradients; the
     selection is one ``ground`` launch (``Switches.native_grounding``; its twin otherwise) and one host read: the counts, then
-    the kept slices."""
+    the kept slices.
+
+    ``nms_threshold``: box NMS (nms.py) of the kept rows at this IoU, one more launch in front of the same host read (now of
+    the counts behind the suppression) -- among all rows of an image, or with ``nms_per_phrase`` only among the rows whose token
+    masks are the same (``phrase_labels``).  The survivors come back in the tail's own order."""
+    from . import nms
+    from .box_ops import box_cxcywh_to_xyxy
     from .transformer import Switches
 
     inputs = [dict(x, captions=preprocess_caption(x["captions"])) for x in batched_inputs]
@@ -189,13 +202,19 @@ def predict(model, batched_inputs, box_threshold, text_threshold, order=0):
             run = ground if Switches.native_grounding else ground_reference
             g = run(prob, out["pred_boxes"], box_threshold, text_threshold, order)
             captions = model._captions(inputs)[0]           # (what the text encoder saw: eval may append learned names)
+            if nms_threshold is not None:
+                labels = phrase_labels(g.token_bits) if nms_per_phrase else None
+                keep, n_nms = nms.nms_padded(box_cxcywh_to_xyxy(g.box), g.score, labels, g.n_keep, nms_threshold)
     finally:
         model.train(was_training)
-    counts = g.n_keep.tolist()
+    if nms_threshold is None:
+        rows = [slice(0, n) for n in g.n_keep.tolist()]
+    else:
+        rows = [keep[b, :n].to(torch.int64).sort().values for b, n in enumerate(n_nms.tolist())]
     results = []
-    for b, n in enumerate(counts):
+    for b, sel in enumerate(rows):
         tokenized = tokenize_caption(model.tokenizer, captions[b])
-        bits = g.token_bits[b, :n].cpu()
-        results.append((g.box[b, :n].cpu(), g.score[b, :n].cpu(),
+        bits = g.token_bits[b, sel].cpu()
+        results.append((g.box[b, sel].cpu(), g.score[b, sel].cpu(),
                         [phrases_from_bits(row, tokenized, captions[b]) for row in bits.tolist()]))
     return results

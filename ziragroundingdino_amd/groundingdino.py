@@ -66,6 +66,9 @@ MODULE_BUILD_FUNCS = _Registry()
 
 
 class GroundingDINO(nn.Module):
+    # postprocess: class-aware NMS (nms.py) of the detections at this IoU; None = none, what the reference's evaluation does
+    nms_threshold_for_evaluation = None
+
     def __init__(self, backbone, transformer, num_queries, aux_loss=False, iter_update=False,
                  query_dim=2, num_feature_levels=1, nheads=8, two_stage_type="no",
                  dec_pred_bbox_embed_share=True, two_stage_class_embed_share=True,
@@ -498,26 +501,41 @@ class GroundingDINO(nn.Module):
 
     def postprocess(self, box_cls, box_pred, batched_inputs, image_sizes):
         """The evaluation tail of ``forward`` (reference :589-602): top-k detections per image, rescaled to the
-        requested output size, clipped, empty boxes dropped."""
-        from . import topk
+        requested output size, clipped, empty boxes dropped.  With ``nms_threshold_for_evaluation`` set, class-aware NMS
+        (nms.py) of what is left, in the same order."""
+        from . import nms, topk
         from .structures import detector_postprocess
         from .transformer import Switches
 
         k = self.select_box_nums_for_evaluation
+        thr = self.nms_threshold_for_evaluation
         if Switches.native_detections and topk.detections_supported(box_cls, box_pred, k):
             # one launch for the batch and one host read (the counts) instead of ~25 launches and a sync per image
             out_sizes = [(inp.get("height", s[0]), inp.get("width", s[1])) for inp, s in zip(batched_inputs, image_sizes)]
             sizes = self._detection_sizes(image_sizes, out_sizes, box_cls.device)
             if sizes is not None:
                 scores, labels, xyxy, n_keep = topk.detections(box_cls.sigmoid(), box_pred, k, sizes)
-                return [{"instances": Instances(osize, pred_boxes=Boxes(xyxy[b, :n]), scores=scores[b, :n],
-                                                pred_classes=labels[b, :n])}
-                        for b, (n, osize) in enumerate(zip(n_keep.tolist(), out_sizes))]
+                if thr is None:
+                    return [{"instances": Instances(osize, pred_boxes=Boxes(xyxy[b, :n]), scores=scores[b, :n],
+                                                    pred_classes=labels[b, :n])}
+                            for b, (n, osize) in enumerate(zip(n_keep.tolist(), out_sizes))]
+                # the suppression reads the counts on the device; the one host read is of the counts behind it
+                keep, n_nms = nms.nms_padded(xyxy, scores, labels, n_keep, thr)
+                processed = []
+                for b, (n, osize) in enumerate(zip(n_nms.tolist(), out_sizes)):
+                    idx = keep[b, :n].to(torch.int64)
+                    processed.append({"instances": Instances(osize, pred_boxes=Boxes(xyxy[b][idx]), scores=scores[b][idx],
+                                                             pred_classes=labels[b][idx])})
+                return processed
         results = self.dt_inference(box_cls, box_pred, image_sizes)
         processed = []
         for r, inp, image_size in zip(results, batched_inputs, image_sizes):
             height, width = inp.get("height", image_size[0]), inp.get("width", image_size[1])
-            processed.append({"instances": detector_postprocess(r, height, width)})
+            r = detector_postprocess(r, height, width)
+            if thr is not None and len(r):
+                keep, n_nms = nms.nms_reference(r.pred_boxes.tensor[None], r.scores[None], r.pred_classes[None], None, thr)
+                r = r[keep[0, :int(n_nms[0])].to(torch.int64)]
+            processed.append({"instances": r})
         return processed
 
     def forward_features(self, features, poss, samples_mask, text_dict, cate_to_token_mask_list,
