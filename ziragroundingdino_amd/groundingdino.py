@@ -68,6 +68,10 @@ MODULE_BUILD_FUNCS = _Registry()
 class GroundingDINO(nn.Module):
     # postprocess: class-aware NMS (nms.py) of the detections at this IoU; None = none, what the reference's evaluation does
     nms_threshold_for_evaluation = None
+    # eval-mode forward: a category list that tokenises longer than max_text_len runs in chunks that fit and the chunks'
+    # detections are merged on the device (vocab.py).  None = one caption, cut at max_text_len as ever; "auto" = split by the
+    # token budget; an int = that, and at most so many names per chunk
+    category_chunk_size = None
 
     def __init__(self, backbone, transformer, num_queries, aux_loss=False, iter_update=False,
                  query_dim=2, num_feature_levels=1, nheads=8, two_stage_type="no",
@@ -477,6 +481,10 @@ class GroundingDINO(nn.Module):
             images = self.preprocess_image(batched_inputs)
             samples = nested_tensor_from_tensor_list(images)
         captions, names_list = self._captions(batched_inputs)
+        if self.category_chunk_size is not None and not self.training and not grounding:
+            chunks = self._category_chunks(names_list)
+            if len(chunks) > 1:      # (a list that is one chunk takes the path below, with its own caption)
+                return self._forward_chunked(batched_inputs, images, samples, chunks)
         finish_text, cate_to_token_mask_list = self.encode_text(captions, samples.device, defer=True)
 
         targets = None
@@ -514,19 +522,7 @@ class GroundingDINO(nn.Module):
             out_sizes = [(inp.get("height", s[0]), inp.get("width", s[1])) for inp, s in zip(batched_inputs, image_sizes)]
             sizes = self._detection_sizes(image_sizes, out_sizes, box_cls.device)
             if sizes is not None:
-                scores, labels, xyxy, n_keep = topk.detections(box_cls.sigmoid(), box_pred, k, sizes)
-                if thr is None:
-                    return [{"instances": Instances(osize, pred_boxes=Boxes(xyxy[b, :n]), scores=scores[b, :n],
-                                                    pred_classes=labels[b, :n])}
-                            for b, (n, osize) in enumerate(zip(n_keep.tolist(), out_sizes))]
-                # the suppression reads the counts on the device; the one host read is of the counts behind it
-                keep, n_nms = nms.nms_padded(xyxy, scores, labels, n_keep, thr)
-                processed = []
-                for b, (n, osize) in enumerate(zip(n_nms.tolist(), out_sizes)):
-                    idx = keep[b, :n].to(torch.int64)
-                    processed.append({"instances": Instances(osize, pred_boxes=Boxes(xyxy[b][idx]), scores=scores[b][idx],
-                                                             pred_classes=labels[b][idx])})
-                return processed
+                return self._padded_instances(*topk.detections(box_cls.sigmoid(), box_pred, k, sizes), out_sizes)
         results = self.dt_inference(box_cls, box_pred, image_sizes)
         processed = []
         for r, inp, image_size in zip(results, batched_inputs, image_sizes):
@@ -537,6 +533,85 @@ class GroundingDINO(nn.Module):
                 r = r[keep[0, :int(n_nms[0])].to(torch.int64)]
             processed.append({"instances": r})
         return processed
+
+    def _padded_instances(self, scores, labels, xyxy, n_keep, out_sizes):
+        """``Instances`` per image from the padded outputs of ``topk.detections`` / ``vocab.merge_detections`` and their
+        counts, behind class-aware NMS where ``nms_threshold_for_evaluation`` is set.  One host read, of the counts."""
+        from . import nms
+
+        thr = self.nms_threshold_for_evaluation
+        if thr is None:
+            return [{"instances": Instances(osize, pred_boxes=Boxes(xyxy[b, :n]), scores=scores[b, :n],
+                                            pred_classes=labels[b, :n])}
+                    for b, (n, osize) in enumerate(zip(n_keep.tolist(), out_sizes))]
+        # the suppression reads the counts on the device; the one host read is of the counts behind it
+        keep, n_nms = nms.nms_padded(xyxy, scores, labels, n_keep, thr)
+        processed = []
+        for b, (n, osize) in enumerate(zip(n_nms.tolist(), out_sizes)):
+            idx = keep[b, :n].to(torch.int64)
+            processed.append({"instances": Instances(osize, pred_boxes=Boxes(xyxy[b][idx]), scores=scores[b][idx],
+                                                     pred_classes=labels[b][idx])})
+        return processed
+
+    def _category_chunks(self, names_list):
+        """The batch's one category list in chunks that fit ``max_text_len`` (vocab.split_categories), remembered per list."""
+        from . import vocab
+
+        names = list(names_list[0])
+        if any(list(other) != names for other in names_list[1:]):
+            raise ValueError("category_chunk_size: the images of a batch must share one category list")
+        size = self.category_chunk_size
+        if not (size == "auto" or (isinstance(size, int) and not isinstance(size, bool) and size >= 1)):
+            raise ValueError("category_chunk_size is None, \"auto\" or a positive int, not %r" % (size,))
+        key = ("category_chunks", tuple(names), size, self.max_text_len)
+        chunks = self._text_cache.get(key)
+        if chunks is None:
+            if len(self._text_cache) >= 64:
+                self._text_cache.clear()
+            chunks = self._text_cache[key] = vocab.split_categories(names, self.tokenizer, self.max_text_len,
+                                                                    None if size == "auto" else size)
+        return chunks
+
+    def _forward_chunked(self, batched_inputs, images, samples, chunks):
+        """Eval-mode ``forward`` for a category list of several chunks: the backbone once; per chunk the text side, the
+        transformer, the heads and the chunk's own top-k (``topk.topk_rows``), whose values and flat indices go into the
+        chunk's slice of the candidate row -- the chunk's [B, Q, C_j] tensor is dead before the next chunk runs; then ONE
+        ``vocab.merge_detections`` call (the global top-k, global labels, the evaluation tail) and the tail of
+        ``postprocess``.  No host read per chunk."""
+        from . import topk, vocab
+
+        features, poss = self.run_backbone(samples)
+        dev, B, k = samples.device, len(batched_inputs), self.select_box_nums_for_evaluation
+        no_padding = getattr(samples, "no_padding", False)
+        cand_scores = cand_index = boxes = None
+        start, classes, offsets = [0], [], []
+        for j, chunk in enumerate(chunks):
+            text_dict, cate_to_token_mask_list, loss_linear_adapter = self.encode_text([vocab.caption_of(chunk)] * B, dev)
+            out = self.forward_features(features, poss, samples.mask, text_dict, cate_to_token_mask_list, loss_linear_adapter,
+                                        None, no_padding=no_padding)
+            C = len(chunk)
+            prob = out["pred_logits"][..., :C].sigmoid()
+            Q = prob.shape[1]
+            if boxes is None:       # every chunk's slice is exactly min(k, Q * C_j) wide: no padding positions
+                widths = [min(k, Q * len(c)) for c in chunks]
+                for w in widths:
+                    start.append(start[-1] + w)
+                cand_scores = torch.empty((B, start[-1]), dtype=prob.dtype, device=prob.device)
+                cand_index = torch.empty((B, start[-1]), dtype=torch.int64, device=prob.device)
+                boxes = torch.empty((len(chunks), B, Q, 4), dtype=out["pred_boxes"].dtype, device=prob.device)
+            val, idx = topk.topk_rows(prob.reshape(B, Q * C), widths[j])
+            cand_scores[:, start[j]:start[j + 1]] = val
+            cand_index[:, start[j]:start[j + 1]] = idx
+            boxes[j] = out["pred_boxes"]
+            offsets.append(sum(classes))
+            classes.append(C)
+        image_sizes = images.image_sizes
+        out_sizes = [(inp.get("height", s[0]), inp.get("width", s[1])) for inp, s in zip(batched_inputs, image_sizes)]
+        sizes = self._detection_sizes(image_sizes, out_sizes, boxes.device)
+        if sizes is None:           # fp32 cannot hold a size: the definition scales by the Python numbers
+            sizes = torch.tensor([[ih, iw, oh, ow] for (ih, iw), (oh, ow) in zip(image_sizes, out_sizes)], dtype=torch.float64)
+        merged = vocab.merge_detections(cand_scores, cand_index, start, classes, offsets, boxes, k, sizes)
+        return self._padded_instances(*merged, out_sizes)
 
     def forward_features(self, features, poss, samples_mask, text_dict, cate_to_token_mask_list,
                          loss_linear_adapter=None, targets=None, no_padding=False, token_logits=False):
