@@ -142,6 +142,27 @@ inline int network_size(int k)
     return P;
 }
 
+// ---- the box arithmetic of the evaluation tail, for every source that puts a query's box into a frame (the tail below,
+// phrasematch.hip): cxcywh in 0..1 -> corners in pixels of the output size, clipped to it.  The float chain is the op chain's,
+// every multiply / add / subtract rounded on its own (sx, sy: fl(out_w / img_w), fl(out_h / img_h)):
+//   xyxy = (cx - 0.5 w, cy - 0.5 h, cx + 0.5 w, cy + 0.5 h);  x *= img_w, y *= img_h;  x *= sx, y *= sy;
+//   x = min(max(x, 0), out_w), y likewise  (fmaxf / fminf: a NaN coordinate clips to 0).
+__device__ __forceinline__ float4 box_to_output(const float4 box, float img_h, float img_w, float sx, float sy, float out_h,
+                                                float out_w)
+{
+#pragma clang fp contract(off)
+    const float hw = __fmul_rn(0.5f, box.z), hh = __fmul_rn(0.5f, box.w);
+    float x0 = __fmul_rn(__fmul_rn(__fsub_rn(box.x, hw), img_w), sx);
+    float y0 = __fmul_rn(__fmul_rn(__fsub_rn(box.y, hh), img_h), sy);
+    float x1 = __fmul_rn(__fmul_rn(__fadd_rn(box.x, hw), img_w), sx);
+    float y1 = __fmul_rn(__fmul_rn(__fadd_rn(box.y, hh), img_h), sy);
+    x0 = fminf(fmaxf(x0, 0.f), out_w);
+    x1 = fminf(fmaxf(x1, 0.f), out_w);
+    y0 = fminf(fmaxf(y0, 0.f), out_h);
+    y1 = fminf(fmaxf(y1, 0.f), out_h);
+    return make_float4(x0, y0, x1, y1);
+}
+
 // ---- the evaluation tail behind a selection (GroundingDINO.dt_inference + structures.detector_postprocess): thread t of
 // image b holds entry t of the selection where `live` (score, label, the address of its cxcywh box); the box goes to pixels
 // of the requested output size, is clipped, and the entries whose box is not empty are compacted into row b of the k-wide
@@ -163,17 +184,9 @@ __device__ __forceinline__ void detections_tail(bool live, float score, int64_t 
     float x0 = 0.f, y0 = 0.f, x1 = 0.f, y1 = 0.f;
     bool keep = false;
     if (live) {
-        const float4 box = *reinterpret_cast<const float4 *>(box_at);
-        const float hw = __fmul_rn(0.5f, box.z), hh = __fmul_rn(0.5f, box.w);
-        x0 = __fmul_rn(__fmul_rn(__fsub_rn(box.x, hw), img_w), sx);
-        y0 = __fmul_rn(__fmul_rn(__fsub_rn(box.y, hh), img_h), sy);
-        x1 = __fmul_rn(__fmul_rn(__fadd_rn(box.x, hw), img_w), sx);
-        y1 = __fmul_rn(__fmul_rn(__fadd_rn(box.y, hh), img_h), sy);
         // (a NaN coordinate ends as a box that is not kept, whatever min / max make of it)
-        x0 = fminf(fmaxf(x0, 0.f), out_w);
-        x1 = fminf(fmaxf(x1, 0.f), out_w);
-        y0 = fminf(fmaxf(y0, 0.f), out_h);
-        y1 = fminf(fmaxf(y1, 0.f), out_h);
+        const float4 px = box_to_output(*reinterpret_cast<const float4 *>(box_at), img_h, img_w, sx, sy, out_h, out_w);
+        x0 = px.x, y0 = px.y, x1 = px.z, y1 = px.w;
         keep = __fsub_rn(x1, x0) > 0.f && __fsub_rn(y1, y0) > 0.f;
     }
     const uint64_t m = __ballot(keep);
