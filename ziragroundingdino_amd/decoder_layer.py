@@ -96,8 +96,8 @@ def applies(layer, tgt, pos, ref, text_lb, memory_value, self_attn_mask, tgt_key
     frozen, heads of width 32, model width 256, no dropout in effect and no masks on the queries."""
     if not (tgt.is_cuda and tgt.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")):
         return False
-    if layer.self_attn is None or not layer.use_text_cross_attention or memory_value is None or pos is None:
-        return False
+    if layer.self_attn is None or not layer.use_text_cross_attention or memory_value is None or pos is None or layer.use_adapter:
+        return False    # (use_adapter: the node contains the FFN, and the adapter joins between the FFN's residual and its LayerNorm)
     if self_attn_mask is not None or tgt_key_padding_mask is not None or pos.requires_grad or ref.requires_grad:
         return False
     if any(p.requires_grad for p in layer.parameters()) or any(p.dtype != torch.float32 for p in layer.parameters()):

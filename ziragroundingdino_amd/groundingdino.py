@@ -5,7 +5,10 @@
 Same surface: ``model(batched_inputs)`` with ``[{"image": uint8/float [3,H,W], "captions":
 "cat . dog .", "instances": Instances}]`` returns the weighted loss dict in training mode
 (``loss_class/_bbox/_giou`` + ``_0.._4`` + ``_enc``, ``loss_conv_adapter``,
-``loss_linear_adapter``) and ``[{"instances": Instances}]`` in eval mode; the hooks
+``loss_linear_adapter``; with ``use_adapter`` and ``use_self_kd`` both on also ``loss_adapter``, the transformer's adapter
+loss times ``loss_adapter_weight`` -- a stated departure: the reference's dual-branch class receives that loss and drops it
+(:532), its sibling classes add it (groundingdino_repconv.py:673-679), and a baseline whose switch does nothing is no
+baseline) and ``[{"instances": Instances}]`` in eval mode; the hooks
 ``before_train`` / ``after_train`` / ``add_cls_prompt`` / ``load_state_dict`` and the
 parameter names (``input_proj_conv_adapter.N.*``, ``rep_linear_adapter.*``, ``feat_map``,
 ``input_proj``, ``bbox_embed``, ``transformer.*``, ``backbone.0.*``, ``bert.*``) are the
@@ -87,7 +90,7 @@ class GroundingDINO(nn.Module):
                  use_cls_linear=False, use_prompt_tuning=False, use_prompt_memory_output=True,
                  use_project_tuning=False, use_project_adapter=True,
                  use_zero_inter_loss_for_conv=True, use_learned_names=False,
-                 bert=None, tokenizer=None, side_branch="rep", **_unused):
+                 bert=None, tokenizer=None, side_branch="rep", use_adapter=False, use_self_kd=False, **_unused):
         super().__init__()
         assert query_dim == 4 and iter_update, "GroundingDINO uses 4-d queries with iterative update"
         assert not use_cls_linear, "use_cls_linear (linear probing ablation) is outside the ZiRa path"
@@ -200,6 +203,7 @@ class GroundingDINO(nn.Module):
         self.use_add_names = use_add_names
         self.select_box_nums_for_evaluation = select_box_nums_for_evaluation
         self.loss_adapter_weight = loss_adapter_weight
+        self.use_adapter, self.use_self_kd = use_adapter, use_self_kd
         self.freeze_all = freeze_all
         self.use_bert_tuning = use_bert_tuning
         self.use_cls_linear = use_cls_linear
@@ -647,12 +651,13 @@ class GroundingDINO(nn.Module):
 
         # (capture under autocast needs the weight-cast cache off, as ZiraTrainer sets it: with the cache on, eager launches)
         autocast_cache = torch.is_autocast_enabled("cuda") and torch.is_autocast_cache_enabled()
+        adapter_loss = None
         if (self.use_transformer_graph and self.training and srcs[0].is_cuda and not autocast_cache
-                and self._frozen(self.transformer) and torch.is_grad_enabled()):
+                and self._frozen(self.transformer) and torch.is_grad_enabled() and not self.use_adapter):
             hs, reference, hs_enc, ref_enc, init_box_proposal = self._graphed_transformer(
                 srcs, masks, poss, text_dict, no_padding=no_padding)
         else:
-            hs, reference, hs_enc, ref_enc, init_box_proposal, _ = self.transformer(
+            hs, reference, hs_enc, ref_enc, init_box_proposal, adapter_loss = self.transformer(
                 srcs, masks, None, poss, None, None, text_dict, no_padding=no_padding)
 
         # Heads (reference groundingdino_dual_zero_rep_branch.py:559-583).  The box MLP is shared by
@@ -730,6 +735,9 @@ class GroundingDINO(nn.Module):
                 key = "loss_language_adapter" if self.side_branch == "multilayer" else "loss_linear_adapter"
                 loss_dict[key] = loss_linear_adapter * self.loss_adapter_weight
                 total = None if total is None else total + loss_dict[key].reshape(())
+            if self.use_adapter and self.use_self_kd:
+                loss_dict["loss_adapter"] = adapter_loss * self.loss_adapter_weight
+                total = None if total is None else total + loss_dict["loss_adapter"].reshape(())
             if total is not None:
                 loss_dict.total = total        # == sum(loss_dict.values()); ZiraTrainer back-propagates this one
             return loss_dict
@@ -874,7 +882,8 @@ def build_dual_zero_rep_branch_groundingdino(args, bert=None, tokenizer=None, si
         use_project_adapter=args.use_project_adapter,
         use_zero_inter_loss_for_conv=args.use_zero_inter_loss_for_conv,
         use_learned_names=args.use_learned_names, device=getattr(args, "device", "cuda"),
-        bert=bert, tokenizer=tokenizer, side_branch=side_branch)
+        bert=bert, tokenizer=tokenizer, side_branch=side_branch, use_adapter=getattr(args, "use_adapter", False),
+        use_self_kd=getattr(args, "use_self_kd", False))
 
 
 @MODULE_BUILD_FUNCS.registe_with_name(module_name="dualzerorepmultilayerbranchgroundingdino")

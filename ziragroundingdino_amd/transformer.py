@@ -7,8 +7,9 @@ Module / parameter names follow the reference so that its checkpoints load uncha
 (SURVEY.md appendix A): ``encoder.layers.N.self_attn.*``, ``encoder.text_layers.N.*``,
 ``encoder.fusion_layers.N.*``, ``decoder.layers.N.{cross_attn,ca_text,self_attn,...}``,
 ``decoder.ref_point_head``, ``level_embed``, ``tgt_embed``, ``enc_output``, ``enc_output_norm``.
-The ablation-only ``use_adapter`` (Adapter / MoE) branch is not part of the ZiRa path
-(``use_adapter = False`` in config/GroundingDINO_SwinT_OGC_rep.py:56) and is not built.
+``use_adapter`` (off in the ZiRa config, config/GroundingDINO_SwinT_OGC_rep.py:56) builds the reference's gated
+``Adapter`` beside the FFN of every deformable encoder / decoder layer (adapter.py): the parameter-efficient baseline ZiRa
+is compared against.  The MoE variant the reference keeps commented out is not built.
 
 Every multi-scale deformable attention call (6 encoder layers with Q = S, 6 decoder layers
 with Q = 900) runs the gfx950 kernels through ``MultiScaleDeformableAttention``.
@@ -178,6 +179,7 @@ class Switches:
     native_detections = True   # GroundingDINO.postprocess: the evaluation tail as one launch + one host read per batch (topk.py)
     native_grounding = True    # grounding.predict: the free-text tail as one launch + one host read per batch (grounding.py); off = its op-chain twin
     native_nms = True          # nms.nms_padded and what stands on it: the suppression as one launch for the batch (csrc/nms.hip); off = nms.nms_reference
+    native_adapter = True      # adapter.Adapter (only with use_adapter): one autograd node over csrc/adapter.hip; off = adapter.adapter_reference
     native_ema = True          # ema.EMAUpdater.update / apply_and_restore: one launch over every fp32 CUDA tensor (csrc/ema.hip); off = the reference's op chain
     # arithmetic of the frozen FFN products on the image-token rows: "f32" = the library's fp32 GEMMs (+ csrc/gemm_drelu.hip);
     # "bf16x3" = fp32-accurate split-bf16 products on the bf16 matrix cores (csrc/gemm_bf16x3.hip, gemm_bf16x3.py);
@@ -766,10 +768,8 @@ class DeformableTransformerEncoderLayer(nn.Module):
     (reference transformer_for_adapter.py:809-907)."""
 
     def __init__(self, d_model=256, d_ffn=1024, dropout=0.1, activation="relu", n_levels=4,
-                 n_heads=8, n_points=4, use_adapter=False, **_unused):
+                 n_heads=8, n_points=4, use_adapter=False, use_self_kd=True, encoder_gate_base_scale=0.1, **_unused):
         super().__init__()
-        if use_adapter:
-            raise NotImplementedError("use_adapter (Adapter/MoE ablation) is outside the ZiRa path")
         self.self_attn = MSDeformAttn(embed_dim=d_model, num_levels=n_levels, num_heads=n_heads,
                                       num_points=n_points, batch_first=True)
         self.dropout1 = nn.Dropout(dropout)
@@ -780,7 +780,11 @@ class DeformableTransformerEncoderLayer(nn.Module):
         self.linear2 = nn.Linear(d_ffn, d_model)
         self.dropout3 = nn.Dropout(dropout)
         self.norm2 = LayerNorm(d_model)
-        self.use_adapter = False
+        self.use_adapter = use_adapter
+        if use_adapter:   # (reference :849-856)
+            from .adapter import Adapter
+            self.adapter = Adapter(embed_dim=d_model, down_dim=64, activation=self.activation, ffn_drop=dropout,
+                                   gate_base_scale=encoder_gate_base_scale, use_gate=True, use_self_kd=use_self_kd)
 
     @staticmethod
     def with_pos_embed(tensor, pos):
@@ -797,10 +801,14 @@ class DeformableTransformerEncoderLayer(nn.Module):
     native_padded = True      # the same node for calls WITH a padding mask (encoder_layer.padded_applies); False: the modules
 
     def forward_ffn(self, src):
+        # (reference :877-886: the adapter reads the FFN's input and joins after the FFN's residual, in front of the LayerNorm)
+        adapter_out, adapter_loss = self.adapter(src) if self.use_adapter else (None, src.new_zeros(1))
         if (self.fuse_bias_relu and self.activation is F.relu and src.is_cuda and src.dtype == torch.float32
                 and (self.dropout2.p == 0.0 or not self.training) and not torch.is_autocast_enabled()):
             x2 = src.reshape(-1, src.shape[-1])
-            if self.dropout3.p == 0.0 and _frozen_ffn_norm_ok(x2, self.linear1, self.linear2, self.norm2):
+            # (the node that folds the LayerNorm into the FFN has no third addend: with an adapter, _FrozenFFN and add_norm)
+            if (adapter_out is None and self.dropout3.p == 0.0
+                    and _frozen_ffn_norm_ok(x2, self.linear1, self.linear2, self.norm2)):
                 return _FrozenFFNNorm.apply(x2, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias,
                                             self.norm2.weight, self.norm2.bias, self.norm2.eps,
                                             _ffn_split(self, x2)).view_as(src), src.new_zeros(1)
@@ -812,7 +820,9 @@ class DeformableTransformerEncoderLayer(nn.Module):
                 src2 = self.linear2(h.view(*src.shape[:-1], -1))
         else:
             src2 = self.linear2(self.dropout2(self.activation(self.linear1(src))))
-        return self.norm2.add_norm(src, self.dropout3(src2)), src.new_zeros(1)   # (residual add inside the LN kernel)
+        if adapter_out is not None:   # (src + src2) + adapter_out, the reference's bracket order
+            return self.norm2.add_norm(src + self.dropout3(src2), adapter_out), adapter_loss
+        return self.norm2.add_norm(src, self.dropout3(src2)), adapter_loss   # (residual add inside the LN kernel)
 
     def forward(self, src, pos, reference_points, spatial_shapes, level_start_index,
                 key_padding_mask=None):
@@ -841,10 +851,8 @@ class DeformableTransformerDecoderLayer(nn.Module):
 
     def __init__(self, d_model=256, d_ffn=1024, dropout=0.1, activation="relu", n_levels=4,
                  n_heads=8, n_points=4, use_text_feat_guide=False, use_text_cross_attention=False,
-                 use_adapter=False, **_unused):
+                 use_adapter=False, use_self_kd=True, decoder_gate_base_scale=0.1, **_unused):
         super().__init__()
-        if use_adapter:
-            raise NotImplementedError("use_adapter (Adapter/MoE ablation) is outside the ZiRa path")
         assert not use_text_feat_guide
         ident_or_drop = lambda: nn.Dropout(dropout) if dropout > 0 else nn.Identity()
         self.cross_attn = MSDeformAttn(embed_dim=d_model, num_levels=n_levels, num_heads=n_heads,
@@ -867,7 +875,11 @@ class DeformableTransformerDecoderLayer(nn.Module):
         self.key_aware_proj = None
         self.use_text_feat_guide = use_text_feat_guide
         self.use_text_cross_attention = use_text_cross_attention
-        self.use_adapter = False
+        self.use_adapter = use_adapter
+        if use_adapter:   # (reference :968-975)
+            from .adapter import Adapter
+            self.adapter = Adapter(embed_dim=d_model, down_dim=64, activation=self.activation, ffn_drop=dropout,
+                                   gate_base_scale=decoder_gate_base_scale, use_gate=True, use_self_kd=use_self_kd)
 
     def rm_self_attn_modules(self):
         self.self_attn = None
@@ -889,7 +901,10 @@ class DeformableTransformerDecoderLayer(nn.Module):
             w.refresh(self)
 
     def forward_ffn(self, tgt):
-        with torch.amp.autocast("cuda", enabled=False):  # reference :1004 keeps the FFN in fp32
+        adapter_out, adapter_loss = None, tgt.new_zeros(1)
+        with torch.amp.autocast("cuda", enabled=False):  # reference :1004 keeps the FFN, and the adapter, in fp32
+            if self.use_adapter:
+                adapter_out, adapter_loss = self.adapter(tgt)
             if (self.fuse_bias_relu and self.activation is F.relu and tgt.is_cuda and tgt.dtype == torch.float32
                     and (getattr(self.dropout3, "p", 0.0) == 0.0 or not self.training)):
                 x2 = tgt.reshape(-1, tgt.shape[-1])
@@ -901,7 +916,10 @@ class DeformableTransformerDecoderLayer(nn.Module):
                     tgt2 = self.linear2(h.view(*tgt.shape[:-1], -1))
             else:
                 tgt2 = self.linear2(self.dropout3(self.activation(self.linear1(tgt))))
-        return self.norm3(tgt + self.dropout4(tgt2)), tgt.new_zeros(1)
+        tgt = tgt + self.dropout4(tgt2)
+        if adapter_out is not None:
+            tgt = tgt + adapter_out
+        return self.norm3(tgt), adapter_loss
 
     def forward(self, tgt, tgt_query_pos=None, tgt_query_sine_embed=None, tgt_key_padding_mask=None,
                 tgt_reference_points=None, memory_text=None, text_attention_mask=None, memory=None,
@@ -1174,7 +1192,8 @@ class Transformer(nn.Module):
                  learnable_tgt_init=False, two_stage_type="no", embed_init_tgt=False,
                  use_text_enhancer=False, use_fusion_layer=False, use_checkpoint=False,
                  use_transformer_ckpt=False, use_text_cross_attention=False, text_dropout=0.1,
-                 fusion_dropout=0.1, fusion_droppath=0.0, use_adapter=False, **_unused):
+                 fusion_dropout=0.1, fusion_droppath=0.0, use_adapter=False, use_self_kd=True,
+                 encoder_gate_base_scale=0.1, decoder_gate_base_scale=0.1, **_unused):
         super().__init__()
         assert query_dim == 4
         assert not normalize_before
@@ -1188,7 +1207,7 @@ class Transformer(nn.Module):
 
         encoder_layer = DeformableTransformerEncoderLayer(
             d_model, dim_feedforward, dropout, activation, num_feature_levels, nhead, enc_n_points,
-            use_adapter=use_adapter)
+            use_adapter=use_adapter, use_self_kd=use_self_kd, encoder_gate_base_scale=encoder_gate_base_scale)
         text_enhance_layer = TransformerEncoderLayer(
             d_model=d_model, nhead=nhead // 2, dim_feedforward=dim_feedforward // 2,
             dropout=text_dropout) if use_text_enhancer else None
@@ -1202,7 +1221,8 @@ class Transformer(nn.Module):
 
         decoder_layer = DeformableTransformerDecoderLayer(
             d_model, dim_feedforward, dropout, activation, num_feature_levels, nhead, dec_n_points,
-            use_text_cross_attention=use_text_cross_attention, use_adapter=use_adapter)
+            use_text_cross_attention=use_text_cross_attention, use_adapter=use_adapter, use_self_kd=use_self_kd,
+            decoder_gate_base_scale=decoder_gate_base_scale)
         self.decoder = TransformerDecoder(
             decoder_layer, num_decoder_layers, LayerNorm(d_model),
             return_intermediate=return_intermediate_dec, d_model=d_model, query_dim=query_dim,
@@ -1210,6 +1230,7 @@ class Transformer(nn.Module):
 
         self.d_model = d_model
         self.nhead = nhead
+        self.use_adapter = use_adapter
         self.dec_layers = num_decoder_layers
         self.num_patterns = num_patterns if isinstance(num_patterns, int) else 0
         if num_feature_levels > 1:
@@ -1335,7 +1356,7 @@ class Transformer(nn.Module):
     def run_decoder(self, tgt, refpoint_embed, memory, mask_flatten, lvl_pos_embed_flatten, spatial_shapes,
                     level_start_index, valid_ratios, text_dict, attn_mask=None, no_padding=False):
         """The six decoder layers on the selected queries (reference :374-400) -> (hs, references)."""
-        hs, references, _ = self.decoder(
+        hs, references, self.__dict__["_decoder_adapter_loss"] = self.decoder(
             tgt=tgt.transpose(0, 1), memory=memory.transpose(0, 1),
             memory_key_padding_mask=None if no_padding else mask_flatten,
             pos=lvl_pos_embed_flatten.transpose(0, 1),
@@ -1383,6 +1404,8 @@ class Transformer(nn.Module):
         hs, references, hs_enc, ref_enc, init_box_proposal = self.select_and_decode(
             memory, mask_flatten, lvl_pos_embed_flatten, shapes, spatial_shapes, level_start_index,
             valid_ratios, text_dict, refpoint_embed, tgt, attn_mask, no_padding=no_padding)
+        if self.use_adapter:   # (reference :415: the encoder's and the decoder's; without adapters both are zeros)
+            adapter_loss1 = adapter_loss1 + self.__dict__.pop("_decoder_adapter_loss")
         return hs, references, hs_enc, ref_enc, init_box_proposal, adapter_loss1
 
 
@@ -1400,4 +1423,6 @@ def build_transformer(args):
         use_transformer_ckpt=args.use_transformer_ckpt,
         use_text_cross_attention=args.use_text_cross_attention, text_dropout=args.text_dropout,
         fusion_dropout=args.fusion_dropout, fusion_droppath=args.fusion_droppath,
-        use_adapter=getattr(args, "use_adapter", False))
+        use_adapter=getattr(args, "use_adapter", False), use_self_kd=getattr(args, "use_self_kd", False),
+        encoder_gate_base_scale=getattr(args, "encoder_gate_base_scale", 0.1),
+        decoder_gate_base_scale=getattr(args, "decoder_gate_base_scale", 0.1))
