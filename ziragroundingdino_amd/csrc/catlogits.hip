@@ -11,6 +11,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "cat_max.h"
 #include "zira_msda.h"
 
 namespace {
@@ -32,12 +33,9 @@ __global__ __launch_bounds__(256) void cat_logits_fwd(const float *__restrict__ 
         const float *lr = logits + row * T;
         const uint8_t *m = mask + ((size_t)b * Cmax + c) * Tmax;
         const int nt = n_tok[b];
-        for (int t = 0; t < nt; ++t) {
-            const float v = lr[t];
-            if (m[t] && v > best) { best = v; at = t; }
-        }
+        for (int t = 0; t < nt; ++t) zira_cat_max_step(m[t] != 0, lr[t], t, best, at);      // (the tie rule: cat_max.h)
     }
-    out[idx] = at >= 0 ? best : for_fill;
+    out[idx] = zira_cat_max_value(best, at, for_fill);
     if (c < Cmax) arg[row * Cmax + c] = at;
 }
 

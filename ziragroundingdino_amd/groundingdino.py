@@ -39,7 +39,7 @@ from .rsb import RepZeroConv2d, RepZeroLinear
 from .structures import Boxes, ImageList, Instances
 from .text_masks import generate_masks_with_special_tokens_and_transfer_map
 from .transformer import build_transformer
-from .utils import (MLP, ContrastiveEmbed, NestedTensor, box_head, inverse_sigmoid,
+from .utils import (MLP, ContrastiveEmbed, ContrastiveEmbedwithLinear, NestedTensor, box_head, inverse_sigmoid,
                     nested_tensor_from_tensor_list, recover_to_cls_logits)
 
 
@@ -93,7 +93,6 @@ class GroundingDINO(nn.Module):
                  bert=None, tokenizer=None, side_branch="rep", use_adapter=False, use_self_kd=False, **_unused):
         super().__init__()
         assert query_dim == 4 and iter_update, "GroundingDINO uses 4-d queries with iterative update"
-        assert not use_cls_linear, "use_cls_linear (linear probing ablation) is outside the ZiRa path"
         assert two_stage_type in ["no", "standard"]
         self.num_queries = num_queries
         self.transformer = transformer
@@ -170,7 +169,10 @@ class GroundingDINO(nn.Module):
 
         # prediction heads, shared across decoder layers
         self.dec_pred_bbox_embed_share = dec_pred_bbox_embed_share
-        _class_embed = ContrastiveEmbed(max_text_len=max_text_len)
+        if use_cls_linear:   # linear probing: the classifier gets a trained linear in front of the text product (reference :317-321)
+            _class_embed = ContrastiveEmbedwithLinear(max_text_len=max_text_len, hidden_dim=hidden_dim)
+        else:
+            _class_embed = ContrastiveEmbed(max_text_len=max_text_len)
         _bbox_embed = MLP(hidden_dim, hidden_dim, 4, 3)
         nn.init.constant_(_bbox_embed.layers[-1].weight.data, 0)
         nn.init.constant_(_bbox_embed.layers[-1].bias.data, 0)
@@ -661,15 +663,18 @@ class GroundingDINO(nn.Module):
                 srcs, masks, None, poss, None, None, text_dict, no_padding=no_padding)
 
         # Heads (reference groundingdino_dual_zero_rep_branch.py:559-583).  The box MLP is shared by
-        # the decoder layers and the classifier is parameter-free, so all layers -- and in training
-        # the encoder proposals -- go through them as ONE stacked tensor instead of layer by layer.
+        # the decoder layers and so is the classifier, so all layers go through them as ONE stacked tensor instead
+        # of layer by layer -- and in training the encoder proposals with them: through the same call where the
+        # classifier is parameter-free (a deep copy computes the same thing), through the encoder's own module where
+        # it is trained (use_cls_linear: the copy has weights of its own), joined behind it.
         n_dec = len(hs)
         shared_heads = (all(m is self.bbox_embed[0] for m in self.bbox_embed)
                         and all(m is self.class_embed[0] for m in self.class_embed))
         enc_cls = getattr(self.transformer, "enc_out_class_embed", None)
+        linear_head = isinstance(self.class_embed[0], ContrastiveEmbedwithLinear)
         with_enc = (self.training and hs_enc is not None and shared_heads
-                    and isinstance(enc_cls, ContrastiveEmbed)          # parameter-free: a deep copy
-                    and isinstance(self.class_embed[0], ContrastiveEmbed)  # computes the same thing
+                    and type(enc_cls) is type(self.class_embed[0])
+                    and isinstance(enc_cls, (ContrastiveEmbed, ContrastiveEmbedwithLinear))
                     and enc_cls.max_text_len == self.class_embed[0].max_text_len
                     and hs_enc[-1].shape == hs[0].shape)
         if shared_heads:
@@ -684,7 +689,17 @@ class GroundingDINO(nn.Module):
             outputs_coord_list = torch.stack(outputs_coord_list)
         if token_logits:
             return {"pred_logits": self.class_embed[-1](hs[-1], text_dict), "pred_boxes": outputs_coord_list[-1]}
-        if shared_heads:
+        if shared_heads and linear_head:
+            # linear + text product + fold into category logits: one node per module (utils.ContrastiveEmbedwithLinear)
+            if with_enc and enc_cls is self.class_embed[0]:
+                cls_all = enc_cls.category_logits(torch.cat([hs_all, hs_enc[-1][None]]), text_dict, cate_to_token_mask_list, -100.0)
+            else:
+                cls_all = self.class_embed[0].category_logits(hs_all, text_dict, cate_to_token_mask_list, -100.0)
+                if with_enc:
+                    cls_enc = enc_cls.category_logits(hs_enc[-1], text_dict, cate_to_token_mask_list, -100.0)
+                    cls_all = torch.cat([cls_all, cls_enc[None]])
+            outputs_class = cls_all[:n_dec]
+        elif shared_heads:
             cls_in = torch.cat([hs_all, hs_enc[-1][None]]) if with_enc else hs_all
             cls_all = recover_to_cls_logits(self.class_embed[0](cls_in, text_dict),
                                             cate_to_token_mask_list, for_fill=-100.0)
@@ -703,6 +718,8 @@ class GroundingDINO(nn.Module):
             if hs_enc is not None:
                 if with_enc:
                     interm_class = cls_all[n_dec]
+                elif isinstance(enc_cls, ContrastiveEmbedwithLinear):
+                    interm_class = enc_cls.category_logits(hs_enc[-1], text_dict, cate_to_token_mask_list, -100.0)
                 else:
                     interm_class = self.transformer.enc_out_class_embed(hs_enc[-1], text_dict)
                     interm_class = recover_to_cls_logits(interm_class, cate_to_token_mask_list, for_fill=-100.0)
@@ -834,12 +851,15 @@ class GroundingDINO(nn.Module):
 
     def before_train(self):
         """Freeze everything, then unfreeze what the method trains: every parameter whose name
-        contains "adapter" -- the two side branches and their twins (reference :722-734)."""
+        contains "adapter" -- the two side branches and their twins -- and what the baselines' switches name
+        (reference :722-734)."""
         if self.freeze_all:
             for param in self.parameters():
                 param.requires_grad = False
         if self.use_bert_tuning:
             self.unfreeze_module_(["bert", "feat_map"])
+        if self.use_cls_linear:      # linear probing: both heads are trained, the encoder's copies with them (reference :728-729)
+            self.unfreeze_module_(["class_embed", "bbox_embed"])
         if self.use_prompt_tuning:
             self.unfreeze_module_(["prompt_memory_pool"])
         if self.use_project_tuning:

@@ -6,6 +6,10 @@ uses): ``MLP`` (:171), ``ContrastiveEmbed`` (:234-269), ``recover_to_cls_logits`
 ``gen_encoder_output_proposals`` (:56-116), ``inverse_sigmoid`` (util/misc.py:704-708),
 ``NestedTensor`` / ``nested_tensor_from_tensor_list`` (util/misc.py:440-499).
 
+``ContrastiveEmbedwithLinear`` (:272-310) is the classifier of the linear-probing baseline (``use_cls_linear``): a trained
+linear in front of the text product.  Its head -- linear, text product and the fold into category logits -- is one native
+node over csrc/clslinear.hip (``_ClsLinearLogits``); ``cls_linear_logits_reference`` is the definition in torch ops.
+
 Differences that do not change results: ``recover_to_cls_logits`` is one masked max per image
 instead of a Python loop over categories (the reference loops B x n_cat with boolean indexing,
 each iteration a device sync).
@@ -321,6 +325,183 @@ def recover_to_cls_logits(logits: Tensor, cate_to_token_mask_list: List[Tensor],
         per_cat = per_cat.masked_fill(torch.isneginf(per_cat), for_fill)
         new_logits[..., bid, :, :n_cat] = per_cat
     return new_logits
+
+
+# ---- the trained class head of the linear-probing baseline (``use_cls_linear``) -------------------------------------------------
+
+FORCE_REFERENCE = False      # True: every ContrastiveEmbedwithLinear.category_logits call is cls_linear_logits_reference
+CLS_LINEAR_DIM, CLS_LINEAR_MAX_TOKENS, CLS_LINEAR_MAX_CATEGORIES = 256, 256, 256
+_CLS_LINEAR_WS = {}
+_range_cache = {}
+
+
+def cls_linear_logits_reference(x: Tensor, weight: Tensor, bias: Tensor, text_dict, cate_to_token_mask_list: List[Tensor],
+                                for_fill=float("-inf"), max_text_len=256) -> Tensor:
+    """The definition, in torch ops, of ``recover_to_cls_logits(ContrastiveEmbedwithLinear(x, text_dict),
+    cate_to_token_mask_list, for_fill)`` (reference utils.py:272-320): ``x [..., B, Q, D]`` -> ``[..., B, Q, max_text_len]``.
+
+        z = x W^T + b;   l[.., b, q, t] = <z[.., b, q], text[b, t]>, -inf on padded tokens and out to max_text_len columns;
+        new[.., b, q, c] = max over the tokens of category c of l[.., b, q, t];   for_fill in every other column
+
+    and for a category without tokens (or whose tokens are all padded) ``for_fill`` as well, the rule of
+    ``recover_to_cls_logits`` here: the reference's max over an empty selection raises."""
+    text, text_token_mask = text_dict["encoded_text"], text_dict["text_token_mask"]
+    assert x.shape[-3] == len(cate_to_token_mask_list)
+    res = F.linear(x, weight, bias) @ text.transpose(-1, -2)
+    res = res.masked_fill(~text_token_mask[:, None, :], float("-inf"))
+    pad = max_text_len - res.shape[-1]
+    if pad > 0:
+        res = F.pad(res, (0, pad), value=float("-inf"))
+    new_logits = torch.full(res.shape, for_fill, device=res.device, dtype=res.dtype)
+    for bid, mask in enumerate(cate_to_token_mask_list):          # mask: [n_cat, n_token] bool
+        n_cat, n_tok = mask.shape
+        if n_cat == 0:
+            continue
+        tok = res[..., bid, :, :n_tok]                              # [..., Q, n_tok]
+        per_cat = tok[..., None, :].masked_fill(~mask.to(res.device), float("-inf")).max(dim=-1)[0]
+        per_cat = per_cat.masked_fill(torch.isneginf(per_cat), for_fill)
+        new_logits[..., bid, :, :n_cat] = per_cat
+    return new_logits
+
+
+def _category_token_ranges(masks: List[Tensor], device):
+    """int32 [B, Cmax, 2] on ``device``: per category the first token of its mask row and one past the last (0, 0 for an empty
+    row) -- where the native scan of a category starts and ends; remembered per list object, as ``_packed_category_masks``."""
+    key = (id(masks), str(device))
+    hit = _range_cache.get(key)
+    if hit is not None and hit[0] is masks:
+        return hit[1]
+    cmax = max([m.shape[0] for m in masks] + [0])
+    ranges = torch.zeros((len(masks), max(cmax, 1), 2), dtype=torch.int32)
+    for b, m in enumerate(masks):
+        m = m.to("cpu", torch.bool)
+        if m.numel() == 0:
+            continue
+        idx = torch.arange(1, m.shape[1] + 1, dtype=torch.int32)
+        last = (m * idx).max(dim=1)[0]                                              # one past the last set token, 0 = none
+        first = torch.where(m, idx - 1, torch.full_like(idx, m.shape[1])).min(dim=1)[0]
+        ranges[b, :m.shape[0], 0] = torch.where(last > 0, first, torch.zeros_like(first))
+        ranges[b, :m.shape[0], 1] = last
+    val = ranges.to(device)
+    if len(_range_cache) > 64:
+        _range_cache.clear()
+    _range_cache[key] = (masks, val)
+    return val
+
+
+def cls_linear_native_supported(x: Tensor, weight: Tensor, bias: Tensor, text_dict, masks, max_text_len) -> bool:
+    """Shapes, dtypes and placement csrc/clslinear.hip takes (the switches are the caller's): fp32 CUDA tensors outside autocast,
+    D = 256, at most 256 text tokens and 256 categories, a text that takes no part in autograd."""
+    text, tmask = text_dict["encoded_text"], text_dict["text_token_mask"]
+    if not (x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda") and x.numel() > 0 and x.dim() >= 3):
+        return False
+    if x.shape[-1] != CLS_LINEAR_DIM or tuple(weight.shape) != (CLS_LINEAR_DIM, CLS_LINEAR_DIM) or bias is None:
+        return False
+    if any(t.dtype != torch.float32 or t.device != x.device for t in (weight, bias, text)) or tmask.device != x.device:
+        return False
+    if text.requires_grad and torch.is_grad_enabled():
+        return False
+    B, T = text.shape[0], text.shape[1]
+    if text.dim() != 3 or text.shape[2] != CLS_LINEAR_DIM or x.shape[-3] != B or len(masks) != B or tuple(tmask.shape) != (B, T):
+        return False
+    cmax = max([m.shape[0] for m in masks] + [0])
+    tmax = max([m.shape[1] for m in masks] + [0])
+    if not (1 <= T <= CLS_LINEAR_MAX_TOKENS and 1 <= cmax <= min(CLS_LINEAR_MAX_CATEGORIES, max_text_len) and 1 <= tmax <= max_text_len):
+        return False
+    from . import _lib
+    return _lib.load().zira_cls_linear_workspace_floats(x.numel() // CLS_LINEAR_DIM, CLS_LINEAR_DIM, T, cmax) > 0
+
+
+class _ClsLinearLogits(torch.autograd.Function):
+    """(x [..., B, Q, 256], W, b, text [B, T, 256], ...) -> category logits [..., B, Q, max_text_len] through
+    zira_cls_linear_logits_{fwd,bwd}_f32 (csrc/clslinear.hip): one launch forward, three backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, text, text_token_mask, masks, for_fill, max_text_len):
+        from . import _lib
+
+        lib = _lib.load()
+        dev = x.device
+        x, weight, bias, text = x.contiguous(), weight.contiguous(), bias.contiguous(), text.detach().contiguous()
+        tmask = text_token_mask.to(torch.uint8).contiguous()
+        packed, n_cat, n_tok, cmax, tmax = _packed_category_masks(masks, dev)
+        ranges = _category_token_ranges(masks, dev)
+        B, Q = x.shape[-3], x.shape[-2]
+        R, T = x.numel() // CLS_LINEAR_DIM, text.shape[1]
+        out = torch.empty(x.shape[:-1] + (max_text_len,), dtype=torch.float32, device=dev)
+        arg = torch.empty((R, cmax), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.zira_cls_linear_logits_fwd_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), text.data_ptr(),
+                                                    tmask.data_ptr(), packed.data_ptr(), ranges.data_ptr(), n_cat.data_ptr(),
+                                                    n_tok.data_ptr(), R, B, Q, T, max_text_len, cmax, tmax, float(for_fill),
+                                                    out.data_ptr(), arg.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError("zira_cls_linear_logits_fwd_f32 failed with code %d" % rc)
+        ctx.save_for_backward(x, weight, text, arg, n_cat, n_tok)
+        ctx.dims = (R, B, Q, T, max_text_len, cmax)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import _lib
+        from .adapter import _counter
+        from .dense import _scratch
+
+        lib = _lib.load()
+        x, weight, text, arg, n_cat, n_tok = ctx.saved_tensors
+        R, B, Q, T, T_out, cmax = ctx.dims
+        dev = x.device
+        grad_out = grad_out.contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None       # pure linear probing: x carries no gradient
+        g_w = torch.empty_like(weight)
+        g_b = torch.empty(CLS_LINEAR_DIM, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ws = _scratch(_CLS_LINEAR_WS, dev, lib.zira_cls_linear_workspace_floats(R, CLS_LINEAR_DIM, T, cmax))
+            rc = lib.zira_cls_linear_logits_bwd_f32(grad_out.data_ptr(), arg.data_ptr(), n_cat.data_ptr(), n_tok.data_ptr(),
+                                                    x.data_ptr(), weight.data_ptr(), text.data_ptr(), R, B, Q, T, T_out, cmax,
+                                                    gx.data_ptr() if gx is not None else None, g_w.data_ptr(), g_b.data_ptr(),
+                                                    ws.data_ptr(), _counter(dev).data_ptr(),
+                                                    torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError("zira_cls_linear_logits_bwd_f32 failed with code %d" % rc)
+        return gx, g_w, g_b, None, None, None, None, None
+
+
+class ContrastiveEmbedwithLinear(nn.Module):
+    """The classifier of the linear-probing baseline: ``ContrastiveEmbed`` behind a trained ``hidden_dim x hidden_dim`` linear
+    (reference utils.py:272-310; parameters ``cls_linear.weight``, ``cls_linear.bias``, nn.Linear's default initialisation).
+    ``forward`` is the reference's: token logits.  ``category_logits`` is the head the model calls: the fold into category
+    logits behind it, as ONE native node where csrc/clslinear.hip applies (``transformer.Switches.native_cls_linear``) and as
+    ``cls_linear_logits_reference`` everywhere else -- CPU tensors, other dtypes, autocast, shapes the kernels decline, a text
+    that requires grad, ``FORCE_REFERENCE``."""
+
+    def __init__(self, max_text_len=256, hidden_dim=256):
+        super().__init__()
+        self.max_text_len = max_text_len
+        self.hidden_dim = hidden_dim
+        self.cls_linear = nn.Linear(hidden_dim, hidden_dim)
+
+    def forward(self, x, text_dict):
+        assert isinstance(text_dict, dict)
+        y = text_dict["encoded_text"]
+        text_token_mask = text_dict["text_token_mask"]
+        res = self.cls_linear(x) @ y.transpose(-1, -2)
+        res = res.masked_fill(~text_token_mask[:, None, :], float("-inf"))
+        pad = self.max_text_len - res.shape[-1]
+        if pad > 0:
+            res = F.pad(res, (0, pad), value=float("-inf"))
+        return res
+
+    def category_logits(self, x, text_dict, cate_to_token_mask_list, for_fill=float("-inf")):
+        """``recover_to_cls_logits(self(x, text_dict), cate_to_token_mask_list, for_fill)`` for ``x [..., B, Q, D]``."""
+        from .transformer import Switches
+        w, b = self.cls_linear.weight, self.cls_linear.bias
+        if (Switches.native_cls_linear and not FORCE_REFERENCE
+                and cls_linear_native_supported(x, w, b, text_dict, cate_to_token_mask_list, self.max_text_len)):
+            return _ClsLinearLogits.apply(x, w, b, text_dict["encoded_text"], text_dict["text_token_mask"],
+                                          cate_to_token_mask_list, for_fill, self.max_text_len)
+        return cls_linear_logits_reference(x, w, b, text_dict, cate_to_token_mask_list, for_fill, self.max_text_len)
 
 
 class NestedTensor(object):
