@@ -200,6 +200,7 @@ class GroundingDINO(nn.Module):
         self.pixel_mean, self.pixel_std = pixel_mean, pixel_std
         self._pixel_stats = {}
         self._text_cache = {}
+        self._prompt_tables = {}     # use_prompt_tuning: the substitution's index tables per caption set (prompt.py)
         self.device = device
         self._reset_parameters()
         self.use_add_names = use_add_names
@@ -324,7 +325,9 @@ class GroundingDINO(nn.Module):
             return group_norm_frozen(main, gn, branch), zero_loss
         return gn(main + branch), zero_loss
 
-    def encode_text(self, captions, device, defer=False, hidden_only=False):
+    def encode_text(self, captions, device, defer=False, hidden_only=False, names_list=None):
+        # ``names_list`` (the captions' category names): with ``use_prompt_tuning`` the pool entries of these categories replace
+        # their tokens (project_text); None -- free text, no category list -- substitutes nothing
         # Tokenisation, the sub-sentence masks and their upload are a pure function of the caption
         # strings, and a task trains on one category list for thousands of steps: remembered per
         # (captions, device) instead of redone every step (2.5 ms of host time, five blocking copies).
@@ -378,13 +381,17 @@ class GroundingDINO(nn.Module):
             elif hidden_only and hidden.is_cuda:   # computed on a prefetch stream; the caller has waited for it
                 hidden.record_stream(torch.cuda.current_stream(device))
             text_dict, loss_linear_adapter = self.project_text(
-                hidden, tokenized["attention_mask"].bool(), position_ids, masks)
+                hidden, tokenized["attention_mask"].bool(), position_ids, masks, names_list=names_list,
+                cate_to_token_mask_list=cate_to_token_mask_list, prompt_key=key)
             return text_dict, cate_to_token_mask_list, loss_linear_adapter
 
         return (finish, cate_to_token_mask_list) if defer else finish()
 
-    def project_text(self, bert_hidden, text_token_mask, position_ids, text_self_attention_masks):
-        """feat_map + language side branch (reference :459-476): BERT states -> text_dict."""
+    def project_text(self, bert_hidden, text_token_mask, position_ids, text_self_attention_masks, names_list=None,
+                     cate_to_token_mask_list=None, prompt_key=None):
+        """feat_map + language side branch (reference :459-476): BERT states -> text_dict.  With ``use_prompt_tuning`` and a
+        category list, the pool entries then replace their categories' tokens (the sibling class's groundingdino_dt.py:521-531),
+        in training and in eval, in front of the ``max_text_len`` cut."""
         L = self.max_text_len
         encoded_text = self.feat_map(bert_hidden)
         loss_linear_adapter = None
@@ -394,6 +401,8 @@ class GroundingDINO(nn.Module):
         elif self.use_cet:
             rep_out, loss_linear_adapter = self.rep_linear_adapter(bert_hidden)
             encoded_text = rep_out + encoded_text
+        if self.use_prompt_tuning and names_list is not None and len(self.prompt_memory_pool):
+            encoded_text = self._substitute_prompts(encoded_text, names_list, cate_to_token_mask_list, prompt_key)
         if encoded_text.shape[1] > L:
             encoded_text, text_token_mask = encoded_text[:, :L, :], text_token_mask[:, :L]
             position_ids = position_ids[:, :L]
@@ -402,6 +411,36 @@ class GroundingDINO(nn.Module):
                      "position_ids": position_ids,
                      "text_self_attention_masks": text_self_attention_masks}
         return text_dict, loss_linear_adapter
+
+    def _prompt_names(self, names_list):
+        """``encode_text``'s keyword for the category list: only with ``use_prompt_tuning`` -- without it the call is what it was."""
+        return {"names_list": names_list} if self.use_prompt_tuning else {}
+
+    def _substitute_prompts(self, encoded_text, names_list, cate_to_token_mask_list, prompt_key=None):
+        """``encoded_text`` with the tokens of every category that has a pool entry replaced by the entry (prompt.py).  The index
+        tables are built once per caption set (``prompt_key``: the text cache's key) and pool version -- the one host read of the
+        masks -- and dropped when ``add_cls_prompt`` or ``load_state_dict`` changes the pool."""
+        from . import prompt
+
+        pool = self.prompt_memory_pool
+        wanted = {prompt.pool_key(n) for names in names_list for n in names}
+        keys = [k for k in pool.keys() if k in wanted]
+        if not keys:
+            return encoded_text
+        T = encoded_text.shape[1]
+        key = None if prompt_key is None else (prompt_key, tuple(tuple(names) for names in names_list), T, tuple(keys))
+        table = self._prompt_tables.get(key) if key is not None else None
+        if table is None:
+            for k in keys:
+                if pool[k].dim() != 2 or pool[k].shape[1] != encoded_text.shape[-1]:
+                    raise ValueError("prompt pool entry %s has shape %s, not [n_tok, %d]: it does not come from a prompt-tuning run"
+                                     % (k, tuple(pool[k].shape), encoded_text.shape[-1]))
+            table = prompt.build_table(names_list, cate_to_token_mask_list, keys, [pool[k].shape[0] for k in keys], T)
+            if key is not None:
+                if len(self._prompt_tables) >= 64:
+                    self._prompt_tables.clear()
+                self._prompt_tables[key] = table
+        return prompt.substitute(encoded_text, table, [pool[k] for k in keys])
 
     def _captions(self, batched_inputs):
         captions = [x["captions"] for x in batched_inputs]
@@ -444,7 +483,8 @@ class GroundingDINO(nn.Module):
             captions, names_list = self._captions(batched_inputs)
             overlap, self.overlap_text_and_image = self.overlap_text_and_image, False   # already off the main stream
             try:
-                finish_text, cate_list = self.encode_text(captions, samples.device, defer=True, hidden_only=True)
+                finish_text, cate_list = self.encode_text(captions, samples.device, defer=True, hidden_only=True,
+                                                          **self._prompt_names(names_list))
             finally:
                 self.overlap_text_and_image = overlap
             features, poss = self.run_backbone(samples)
@@ -491,7 +531,8 @@ class GroundingDINO(nn.Module):
             chunks = self._category_chunks(names_list)
             if len(chunks) > 1:      # (a list that is one chunk takes the path below, with its own caption)
                 return self._forward_chunked(batched_inputs, images, samples, chunks)
-        finish_text, cate_to_token_mask_list = self.encode_text(captions, samples.device, defer=True)
+        finish_text, cate_to_token_mask_list = self.encode_text(captions, samples.device, defer=True,
+                                                                **({} if grounding else self._prompt_names(names_list)))
 
         targets = None
         if self.training:
@@ -592,7 +633,8 @@ class GroundingDINO(nn.Module):
         cand_scores = cand_index = boxes = None
         start, classes, offsets = [0], [], []
         for j, chunk in enumerate(chunks):
-            text_dict, cate_to_token_mask_list, loss_linear_adapter = self.encode_text([vocab.caption_of(chunk)] * B, dev)
+            text_dict, cate_to_token_mask_list, loss_linear_adapter = self.encode_text([vocab.caption_of(chunk)] * B, dev,
+                                                                                       **self._prompt_names([list(chunk)] * B))
             out = self.forward_features(features, poss, samples.mask, text_dict, cate_to_token_mask_list, loss_linear_adapter,
                                         None, no_padding=no_padding)
             C = len(chunk)
@@ -839,15 +881,48 @@ class GroundingDINO(nn.Module):
                     continue
                 self.prompt_memory_pool[class_name] = nn.Parameter(v)
                 self.learned_classes.append(class_name[1:-1])
+                self._prompt_tables.clear()
         return super().load_state_dict(state_dict=state_dict, strict=strict)
 
-    def add_cls_prompt(self, class_names, device="cpu", fixed_name=False):
+    def add_cls_prompt(self, class_names, device=None, fixed_name=False):
+        """Pool entries for ``class_names``; entries that exist are kept.  Without ``use_prompt_tuning`` an entry is a random
+        ``[hidden_dim]`` vector on ``device`` (default "cpu") that nothing reads.  With it (the sibling class's
+        groundingdino_dt.py:379-437) an entry is ``[n_tok, hidden_dim]``: the class's rows of the encoded caption
+        ``".".join(class_names) + "."`` -- one trained row per token, initialised from what the frozen model would have seen --
+        on ``device`` (default: where the model is).  A class whose tokens reach behind ``max_text_len`` raises ``ValueError``."""
+        if self.use_prompt_tuning:
+            return self._add_cls_prompt_rows(list(class_names), device, fixed_name)
+        device = "cpu" if device is None else device
         for class_name in class_names:
             self.learned_classes.append(class_name)
             if not fixed_name:
                 class_name = "-{}-".format(class_name)
             if class_name not in self.prompt_memory_pool:
                 self.prompt_memory_pool[class_name] = nn.Parameter(torch.randn(self.hidden_dim).to(device))
+
+    def _add_cls_prompt_rows(self, class_names, device, fixed_name):
+        self.learned_classes.extend(class_names)
+        self._prompt_tables.clear()
+        if not class_names:
+            return
+        model_device = next(self.parameters()).device
+        with torch.no_grad():       # one text pass, no substitution (no category list is handed in)
+            text_dict, cate_to_token_mask_list, _ = self.encode_text([".".join(class_names) + "."], model_device)
+        encoded_text, masks = text_dict["encoded_text"][0], cate_to_token_mask_list[0]
+        T = encoded_text.shape[0]
+        if masks.shape[0] != len(class_names):
+            raise ValueError("add_cls_prompt: the caption of %d class names tokenises into %d categories (an empty name, or one "
+                             "holding a separator?)" % (len(class_names), masks.shape[0]))
+        masks = masks.to("cpu")       # the one host read; the reference indexes with the masks, which reads them too
+        for class_name, mask in zip(class_names, masks):
+            if bool(mask[T:].any()) or not bool(mask.any()):
+                raise ValueError("add_cls_prompt: class %r has %s: it gets no prompt" % (
+                    class_name, "tokens behind max_text_len = %d" % self.max_text_len if bool(mask.any()) else "no tokens"))
+        for class_name, mask in zip(class_names, masks):       # (nothing is created where a class raises)
+            key = class_name if fixed_name else "-{}-".format(class_name)
+            if key not in self.prompt_memory_pool:
+                rows = encoded_text[mask[:T].to(encoded_text.device)].detach().clone()
+                self.prompt_memory_pool[key] = nn.Parameter(rows.to(model_device if device is None else device))
 
     def before_train(self):
         """Freeze everything, then unfreeze what the method trains: every parameter whose name

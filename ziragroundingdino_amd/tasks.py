@@ -164,6 +164,10 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
                 model.ema_state.to(device)
         return final, _evaluate(evaluate, model, spec)
     model = load_model(build_model, init_checkpoint, device)
+    if getattr(model, "use_prompt_tuning", False):
+        # prompt tuning trains the pool entries of this task's classes: they exist before the trainer builds its gradient bucket
+        # and optimizer over the trainable tensors (the reference's do_train, train_multidatasets.py:393-394)
+        model.add_cls_prompt(list(spec.categories_names))
     writers = []
     if spec.log_period is not None and _is_main(process_group):      # (:436-459: the writers are the main process's)
         from . import metrics
