@@ -13,14 +13,11 @@
 #include <stdint.h>
 
 #include "zira_prompt.h"
+#include "prompt_table.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kThreads / kWave;
-
-typedef float f4 __attribute__((ext_vector_type(4)));   // 16 bytes, 16-byte aligned
+using namespace prompt_table;      // kThreads, kWave, kWavesPerBlock, f4, pool_row_of, aligned*, blocks_of
 
 __global__ __launch_bounds__(kThreads) void prompt_fwd_kernel(const float *__restrict__ x, const int32_t *__restrict__ table,
                                                               const zira_prompt_segment *__restrict__ segments, int n_pos, int D,
@@ -29,12 +26,8 @@ __global__ __launch_bounds__(kThreads) void prompt_fwd_kernel(const float *__res
     const int pos = blockIdx.x * kWavesPerBlock + (int)(threadIdx.x / kWave);
     if (pos >= n_pos) return;
     const int lane = threadIdx.x % kWave;
-    const int seg = table[2 * pos], row = table[2 * pos + 1];
-    const float *src = x + (size_t)pos * D;
-    if (seg >= 0 && seg < n_segments && row >= 0) {
-        const zira_prompt_segment s = segments[seg];
-        if (row < s.rows) src = static_cast<const float *>(s.param) + (size_t)row * D;
-    }
+    const float *row = pool_row_of(table, segments, pos, D, n_segments);
+    const float *src = row != nullptr ? row : x + (size_t)pos * D;
     float *dst = out + (size_t)pos * D;
     for (int v = lane; v < D / 4; v += kWave)
         *reinterpret_cast<f4 *>(dst + 4 * v) = *reinterpret_cast<const f4 *>(src + 4 * v);
@@ -74,9 +67,6 @@ __global__ __launch_bounds__(kThreads) void prompt_bwd_kernel(const float *__res
     }
 }
 
-bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
-bool aligned4(const void *p) { return p != nullptr && ((uintptr_t)p & 3) == 0; }
-
 }  // namespace
 
 extern "C" int zira_prompt_supported(int B, int T, int D, int n_segments, long long n_rows)
@@ -89,10 +79,9 @@ extern "C" int zira_prompt_substitute_fwd_f32(const float *x, const int32_t *tab
                                               int T, int D, int n_segments, float *out, void *stream)
 {
     if (!zira_prompt_supported(B, T, D, n_segments, 1)) return -1;
-    if (!aligned16(x) || !aligned16(out) || !aligned4(table) || segments == nullptr || ((uintptr_t)segments & 7) != 0) return -1;
+    if (!aligned16(x) || !aligned16(out) || !aligned4(table) || !aligned8(segments)) return -1;
     const int n_pos = B * T;
-    const unsigned grid = (unsigned)((n_pos + kWavesPerBlock - 1) / kWavesPerBlock);
-    hipLaunchKernelGGL(prompt_fwd_kernel, dim3(grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), x, table, segments,
+    hipLaunchKernelGGL(prompt_fwd_kernel, dim3(blocks_of(n_pos)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), x, table, segments,
                        n_pos, D, n_segments, out);
     return (int)hipGetLastError();
 }
@@ -107,8 +96,7 @@ extern "C" int zira_prompt_substitute_bwd_f32(const float *grad_out, const int32
     if (gx != nullptr && !aligned16(gx)) return -1;
     const int n_pos = B * T;
     const long long units = n_rows + (gx != nullptr ? n_pos : 0);
-    const unsigned grid = (unsigned)((units + kWavesPerBlock - 1) / kWavesPerBlock);
-    hipLaunchKernelGGL(prompt_bwd_kernel, dim3(grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), grad_out, table,
+    hipLaunchKernelGGL(prompt_bwd_kernel, dim3(blocks_of(units)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), grad_out, table,
                        occ_start, occ, n_pos, D, (int)n_rows, n_occ, g_pool, gx);
     return (int)hipGetLastError();
 }

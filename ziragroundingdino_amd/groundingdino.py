@@ -200,7 +200,8 @@ class GroundingDINO(nn.Module):
         self.pixel_mean, self.pixel_std = pixel_mean, pixel_std
         self._pixel_stats = {}
         self._text_cache = {}
-        self._prompt_tables = {}     # use_prompt_tuning: the substitution's index tables per caption set (prompt.py)
+        self._prompt_tables = {}     # use_prompt_tuning / use_prompt_memory: the index tables per caption set (prompt.py)
+        self._replay_cache = None    # replay_memory: the frozen BERT's states of the learned classes' captions
         self.device = device
         self._reset_parameters()
         self.use_add_names = use_add_names
@@ -325,9 +326,8 @@ class GroundingDINO(nn.Module):
             return group_norm_frozen(main, gn, branch), zero_loss
         return gn(main + branch), zero_loss
 
-    def encode_text(self, captions, device, defer=False, hidden_only=False, names_list=None):
-        # ``names_list`` (the captions' category names): with ``use_prompt_tuning`` the pool entries of these categories replace
-        # their tokens (project_text); None -- free text, no category list -- substitutes nothing
+    def _encoder_inputs(self, captions, device):
+        """(tokenized, masks, position_ids, cate_to_token_mask_list, enc_in) of ``captions`` on ``device``."""
         # Tokenisation, the sub-sentence masks and their upload are a pure function of the caption
         # strings, and a task trains on one category list for thousands of steps: remembered per
         # (captions, device) instead of redone every step (2.5 ms of host time, five blocking copies).
@@ -352,10 +352,21 @@ class GroundingDINO(nn.Module):
             if len(self._text_cache) >= 64:
                 self._text_cache.clear()
             cached = self._text_cache[key] = (tokenized, masks, position_ids, cate_to_token_mask_list, dict(enc_in))
-        tokenized, masks, position_ids, cate_to_token_mask_list, enc_in = cached
+        return cached
+
+    def encode_text(self, captions, device, defer=False, hidden_only=False, names_list=None, bert_hidden=None):
+        # ``names_list`` (the captions' category names): with ``use_prompt_tuning`` the pool entries of these categories replace
+        # their tokens (project_text), with ``use_prompt_memory`` they are the memory loss's targets in training and replace
+        # their tokens in eval; None -- free text, no category list -- substitutes nothing and computes no memory loss
+        # ``bert_hidden``: the text encoder's states for these captions where the caller holds them (replay_memory, frozen
+        # BERT): the encoder is not run
+        key = (tuple(captions), str(device))
+        tokenized, masks, position_ids, cate_to_token_mask_list, enc_in = self._encoder_inputs(captions, device)
         enc_in = dict(enc_in)
         side = None
-        if self._frozen(self.bert):
+        if bert_hidden is not None:
+            hidden = bert_hidden
+        elif self._frozen(self.bert):
             if self.use_frontend_graphs and enc_in["input_ids"].is_cuda:
                 if defer and self.overlap_text_and_image:
                     # the frozen BERT (a graph of ~300 launch-bound kernels) runs beside the frozen Swin: its replay
@@ -391,7 +402,18 @@ class GroundingDINO(nn.Module):
                      cate_to_token_mask_list=None, prompt_key=None):
         """feat_map + language side branch (reference :459-476): BERT states -> text_dict.  With ``use_prompt_tuning`` and a
         category list, the pool entries then replace their categories' tokens (the sibling class's groundingdino_dt.py:521-531),
-        in training and in eval, in front of the ``max_text_len`` cut."""
+        in training and in eval, in front of the ``max_text_len`` cut.
+
+        With ``use_cet and use_prompt_memory`` (the sibling class's text-memory replay) and a category list:
+
+        * in training, ``text_dict["loss_prompt_memory"]`` is the L1 distance (mean) between the encoded text behind the side
+          branch and its copy with the rows of every category in ``learned_classes`` overwritten by the stored entry (:509-519),
+          taken in front of any substitution and of the cut; ``forward_features`` takes the key out again;
+        * in eval, with ``use_prompt_memory_output`` as well, the stored rows replace the tokens of every category that has an
+          entry (:521-531).  Two departures from groundingdino_dt.py: ``use_prompt_memory_output`` alone does nothing (its
+          default here is True, and making it live by itself would change every existing evaluation), and the side branch keeps
+          running in eval (the dual-branch class this package mirrors always runs it; after the merge it is the 1e-8
+          initialisation)."""
         L = self.max_text_len
         encoded_text = self.feat_map(bert_hidden)
         loss_linear_adapter = None
@@ -401,7 +423,11 @@ class GroundingDINO(nn.Module):
         elif self.use_cet:
             rep_out, loss_linear_adapter = self.rep_linear_adapter(bert_hidden)
             encoded_text = rep_out + encoded_text
-        if self.use_prompt_tuning and names_list is not None and len(self.prompt_memory_pool):
+        loss_prompt_memory = None
+        if self.use_cet and self.use_prompt_memory and self.training and names_list is not None:
+            loss_prompt_memory = self._prompt_memory_loss(encoded_text, names_list, cate_to_token_mask_list, prompt_key)
+        substitutes = self.use_prompt_tuning or (self.use_prompt_memory and self.use_prompt_memory_output and not self.training)
+        if substitutes and names_list is not None and len(self.prompt_memory_pool):
             encoded_text = self._substitute_prompts(encoded_text, names_list, cate_to_token_mask_list, prompt_key)
         if encoded_text.shape[1] > L:
             encoded_text, text_token_mask = encoded_text[:, :L, :], text_token_mask[:, :L]
@@ -410,11 +436,52 @@ class GroundingDINO(nn.Module):
         text_dict = {"encoded_text": encoded_text, "text_token_mask": text_token_mask,
                      "position_ids": position_ids,
                      "text_self_attention_masks": text_self_attention_masks}
+        if loss_prompt_memory is not None:
+            text_dict["loss_prompt_memory"] = loss_prompt_memory
         return text_dict, loss_linear_adapter
 
     def _prompt_names(self, names_list):
-        """``encode_text``'s keyword for the category list: only with ``use_prompt_tuning`` -- without it the call is what it was."""
-        return {"names_list": names_list} if self.use_prompt_tuning else {}
+        """``encode_text``'s keyword for the category list: only with ``use_prompt_tuning`` or ``use_prompt_memory`` -- without
+        them the call is what it was."""
+        return {"names_list": names_list} if (self.use_prompt_tuning or self.use_prompt_memory) else {}
+
+    def _prompt_table(self, names_list, cate_to_token_mask_list, keys, T, D, prompt_key):
+        """The index tables (prompt.py) of ``names_list`` against the pool entries ``keys``: built once per caption set
+        (``prompt_key``: the text cache's key) and pool version -- the one host read of the masks -- and dropped when
+        ``add_cls_prompt`` or ``load_state_dict`` changes the pool."""
+        from . import prompt
+
+        pool = self.prompt_memory_pool
+        key = None if prompt_key is None else (prompt_key, tuple(tuple(names) for names in names_list), T, tuple(keys))
+        table = self._prompt_tables.get(key) if key is not None else None
+        if table is None:
+            for k in keys:
+                if pool[k].dim() != 2 or pool[k].shape[1] != D:
+                    raise ValueError("prompt pool entry %s has shape %s, not [n_tok, %d]: it does not come from a prompt-tuning or "
+                                     "prompt-memory run" % (k, tuple(pool[k].shape), D))
+            table = prompt.build_table(names_list, cate_to_token_mask_list, keys, [pool[k].shape[0] for k in keys], T)
+            if key is not None:
+                if len(self._prompt_tables) >= 64:
+                    self._prompt_tables.clear()
+                self._prompt_tables[key] = table
+        return table
+
+    def _prompt_memory_loss(self, encoded_text, names_list, cate_to_token_mask_list, prompt_key=None):
+        """``loss_prompt_memory`` (groundingdino_dt.py:509-519): the categories of ``names_list`` that are in ``learned_classes``
+        are pulled back to their stored rows.  A learned class without an entry raises, as the reference's lookup does."""
+        from . import prompt
+
+        pool = self.prompt_memory_pool
+        learned = set(self.learned_classes)
+        wanted = {prompt.pool_key(n) for names in names_list for n in names if n in learned}
+        missing = sorted(k for k in wanted if k not in pool)
+        if missing:
+            raise KeyError("use_prompt_memory: learned classes without a pool entry: %s" % ", ".join(missing))
+        keys = [k for k in pool.keys() if k in wanted]
+        if not keys:      # nothing learned yet (the first task): target == encoded_text
+            return prompt.memory_loss_reference(encoded_text, (names_list, cate_to_token_mask_list), {})
+        table = self._prompt_table(names_list, cate_to_token_mask_list, keys, encoded_text.shape[1], encoded_text.shape[-1], prompt_key)
+        return prompt.memory_loss(encoded_text, table, [pool[k] for k in keys])
 
     def _substitute_prompts(self, encoded_text, names_list, cate_to_token_mask_list, prompt_key=None):
         """``encoded_text`` with the tokens of every category that has a pool entry replaced by the entry (prompt.py).  The index
@@ -427,19 +494,7 @@ class GroundingDINO(nn.Module):
         keys = [k for k in pool.keys() if k in wanted]
         if not keys:
             return encoded_text
-        T = encoded_text.shape[1]
-        key = None if prompt_key is None else (prompt_key, tuple(tuple(names) for names in names_list), T, tuple(keys))
-        table = self._prompt_tables.get(key) if key is not None else None
-        if table is None:
-            for k in keys:
-                if pool[k].dim() != 2 or pool[k].shape[1] != encoded_text.shape[-1]:
-                    raise ValueError("prompt pool entry %s has shape %s, not [n_tok, %d]: it does not come from a prompt-tuning run"
-                                     % (k, tuple(pool[k].shape), encoded_text.shape[-1]))
-            table = prompt.build_table(names_list, cate_to_token_mask_list, keys, [pool[k].shape[0] for k in keys], T)
-            if key is not None:
-                if len(self._prompt_tables) >= 64:
-                    self._prompt_tables.clear()
-                self._prompt_tables[key] = table
+        table = self._prompt_table(names_list, cate_to_token_mask_list, keys, encoded_text.shape[1], encoded_text.shape[-1], prompt_key)
         return prompt.substitute(encoded_text, table, [pool[k] for k in keys])
 
     def _captions(self, batched_inputs):
@@ -669,6 +724,7 @@ class GroundingDINO(nn.Module):
         encodings, ``samples_mask``: [B,H,W] padding mask of the input images.  ``token_logits`` (eval mode): the last
         layer's per-token logits and boxes, without the fold into category logits (``forward_grounding``)."""
         assert not (token_logits and self.training), "token logits are an eval-mode output"
+        loss_prompt_memory = text_dict.pop("loss_prompt_memory", None)      # (project_text, use_prompt_memory; else absent)
         poss = list(poss)
         srcs, masks, loss_conv_adapter = [], [], None
 
@@ -794,6 +850,11 @@ class GroundingDINO(nn.Module):
                 key = "loss_language_adapter" if self.side_branch == "multilayer" else "loss_linear_adapter"
                 loss_dict[key] = loss_linear_adapter * self.loss_adapter_weight
                 total = None if total is None else total + loss_dict[key].reshape(())
+            if self.use_cet and self.use_prompt_memory:       # weight 1 (groundingdino_dt.py:649-650)
+                if loss_prompt_memory is None:
+                    raise RuntimeError("use_prompt_memory: the text side was encoded without the category list (names_list)")
+                loss_dict["loss_prompt_memory"] = loss_prompt_memory
+                total = None if total is None else total + loss_prompt_memory.reshape(())
             if self.use_adapter and self.use_self_kd:
                 loss_dict["loss_adapter"] = adapter_loss * self.loss_adapter_weight
                 total = None if total is None else total + loss_dict["loss_adapter"].reshape(())
@@ -874,23 +935,29 @@ class GroundingDINO(nn.Module):
                     print("unfreeze:", name)
 
     def load_state_dict(self, state_dict, strict=True):
+        self._replay_cache = None      # (the kept BERT states of replay_memory depend on the weights)
         for k, v in state_dict.items():
             if "prompt_memory_pool" in k:
                 class_name = k.split(".")[-1]
                 if class_name == "prompt_memory_pool":
                     continue
-                self.prompt_memory_pool[class_name] = nn.Parameter(v)
+                # (use_prompt_memory without use_prompt_tuning: the entries are memory, not parameters to train)
+                self.prompt_memory_pool[class_name] = nn.Parameter(v, requires_grad=self._pool_trains())
                 self.learned_classes.append(class_name[1:-1])
                 self._prompt_tables.clear()
+                self._replay_cache = None
         return super().load_state_dict(state_dict=state_dict, strict=strict)
 
     def add_cls_prompt(self, class_names, device=None, fixed_name=False):
-        """Pool entries for ``class_names``; entries that exist are kept.  Without ``use_prompt_tuning`` an entry is a random
-        ``[hidden_dim]`` vector on ``device`` (default "cpu") that nothing reads.  With it (the sibling class's
-        groundingdino_dt.py:379-437) an entry is ``[n_tok, hidden_dim]``: the class's rows of the encoded caption
-        ``".".join(class_names) + "."`` -- one trained row per token, initialised from what the frozen model would have seen --
-        on ``device`` (default: where the model is).  A class whose tokens reach behind ``max_text_len`` raises ``ValueError``."""
-        if self.use_prompt_tuning:
+        """Pool entries for ``class_names``; entries that exist are kept.  Without ``use_prompt_tuning`` and
+        ``use_prompt_memory`` an entry is a random ``[hidden_dim]`` vector on ``device`` (default "cpu") that nothing reads.  With
+        either (the sibling class's groundingdino_dt.py:379-437) an entry is ``[n_tok, hidden_dim]``: the class's rows of the
+        encoded caption ``".".join(class_names) + "."`` -- with prompt tuning one trained row per token, initialised from what the
+        frozen model would have seen; with the prompt memory alone a frozen copy (``requires_grad = False``: memory, not a
+        parameter to train, so it stays out of the trainer's bucket and optimizer), taken with the side branch as it stands
+        (``ZiraTrainer.after_train`` calls this before the merge, :419-423) -- on ``device`` (default: where the model is).  A
+        class whose tokens reach behind ``max_text_len`` raises ``ValueError``."""
+        if self.use_prompt_tuning or self.use_prompt_memory:
             return self._add_cls_prompt_rows(list(class_names), device, fixed_name)
         device = "cpu" if device is None else device
         for class_name in class_names:
@@ -903,6 +970,7 @@ class GroundingDINO(nn.Module):
     def _add_cls_prompt_rows(self, class_names, device, fixed_name):
         self.learned_classes.extend(class_names)
         self._prompt_tables.clear()
+        self._replay_cache = None
         if not class_names:
             return
         model_device = next(self.parameters()).device
@@ -922,7 +990,12 @@ class GroundingDINO(nn.Module):
             key = class_name if fixed_name else "-{}-".format(class_name)
             if key not in self.prompt_memory_pool:
                 rows = encoded_text[mask[:T].to(encoded_text.device)].detach().clone()
-                self.prompt_memory_pool[key] = nn.Parameter(rows.to(model_device if device is None else device))
+                self.prompt_memory_pool[key] = nn.Parameter(rows.to(model_device if device is None else device),
+                                                            requires_grad=self._pool_trains())
+
+    def _pool_trains(self):
+        """Pool entries are trained parameters except under ``use_prompt_memory`` alone, where they are stored memory."""
+        return self.use_prompt_tuning or not self.use_prompt_memory
 
     def before_train(self):
         """Freeze everything, then unfreeze what the method trains: every parameter whose name
@@ -946,6 +1019,54 @@ class GroundingDINO(nn.Module):
         for module in self.modules():
             if hasattr(module, "__rep__"):
                 module.__rep__()
+
+    def replay_parameter_prefixes(self):
+        """Name prefixes of the parameters ``replay_memory``'s losses reach: the language side branch with its twin, and -- where
+        their switches make them trainable -- the text encoder, ``feat_map`` and the pool entries."""
+        branch = "rep_language_adapter." if self.side_branch == "multilayer" else "rep_linear_adapter."
+        return (branch, "bert.", "feat_map.", "prompt_memory_pool.")
+
+    def replay_memory(self):
+        """One iteration's losses of the text-only replay stage (groundingdino_dt.py ``replay_memory`` :786-838; it takes no
+        images): the captions of all learned classes are encoded -- feat_map + side branch -- and pulled back to the stored rows.
+        Returns ``{"loss_prompt_memory": 0.5 * loss}`` and, with ``use_zero_inter_loss``, the side branch's zero-interference
+        term times ``loss_adapter_weight`` under the key the training forward uses for it (``loss_linear_adapter`` /
+        ``loss_language_adapter``; the reference's name ``loss_adapter_text`` belongs to a module this class does not have).
+
+        The captions are ``vocab.split_categories(learned_classes)``: J = 1 is the reference's single caption
+        ``".".join(learned) + "."``; J > 1 -- a departure -- is this package's answer to lists longer than ``max_text_len``,
+        which the reference feeds to BERT uncut; they are encoded as one batch of J rows.  A class listed twice in
+        ``learned_classes`` is replayed once.  With BERT frozen its states for these captions are constant: they are computed
+        once per (learned classes, device) and kept, so an iteration is ``project_text`` + the loss."""
+        from . import vocab
+
+        if not (self.use_cet and self.use_prompt_memory and self.training):
+            raise RuntimeError("replay_memory needs use_cet and use_prompt_memory, in training mode")
+        learned = list(dict.fromkeys(self.learned_classes))
+        if not learned:
+            raise RuntimeError("replay_memory: learned_classes is empty -- nothing was stored to replay")
+        missing = [c for c in learned if "-{}-".format(c) not in self.prompt_memory_pool]
+        if missing:
+            raise KeyError("replay_memory: learned classes without a pool entry: %s" % ", ".join(missing))
+        device = next(self.parameters()).device
+        key = (tuple(learned), str(device), self.max_text_len)
+        cached = self._replay_cache
+        if cached is None or cached[0] != key:
+            chunks = vocab.split_categories(learned, self.tokenizer, self.max_text_len)
+            cached = self._replay_cache = [key, [vocab.caption_of(c) for c in chunks], [list(c) for c in chunks], None]
+        _, captions, names_list, hidden = cached
+        frozen = self._frozen(self.bert)
+        if not frozen:
+            hidden = cached[3] = None      # (a trained BERT's states change; none are kept, also for when it is frozen again)
+        elif hidden is None:
+            with torch.no_grad():
+                hidden = cached[3] = self._bert_hidden(dict(self._encoder_inputs(captions, device)[4]))
+        text_dict, _, loss_linear_adapter = self.encode_text(captions, device, names_list=names_list, bert_hidden=hidden)
+        losses = {"loss_prompt_memory": text_dict.pop("loss_prompt_memory") * 0.5}
+        if self.use_zero_inter_loss:
+            name = "loss_language_adapter" if self.side_branch == "multilayer" else "loss_linear_adapter"
+            losses[name] = loss_linear_adapter.reshape(()) * self.loss_adapter_weight
+        return losses
 
     def side_branch_parameters(self):
         """The only tensors that ever receive gradients in ZiRa (4 622 853 values for Swin-T)."""

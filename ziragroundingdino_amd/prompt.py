@@ -15,6 +15,11 @@ several launches per pair, and the same again backward.  Here the masks are read
   autograd then accumulates into each leaf's ``.grad`` as it does for any node: one launch per entry named in the captions.
 * ``substitute_reference`` is the definition in torch ops: from the masks it is the loop itself, from a table it is one
   indexed write.  It serves CPU tensors, other dtypes, autocast, shapes the header declines and ``FORCE_REFERENCE``.
+
+The text-memory replay (``use_prompt_memory``) reads the same tables: ``memory_loss`` is the reference's ``loss_prompt_memory``
+(:509-519, ``replay_memory`` :824-834), ``L1Loss(mean)`` between the encoded text and its copy with the learned categories' rows
+replaced by their stored entries -- one autograd node over csrc/prompt_memory.hip (C ABI in include/zira_prompt_memory.h) that
+returns the scalar, under ``transformer.Switches.native_prompt_memory``; ``memory_loss_reference`` is its definition in torch ops.
 """
 from typing import Mapping, Sequence
 
@@ -48,7 +53,7 @@ class PromptTable:
         self.row_start = [0]
         for r in self.rows:
             self.row_start.append(self.row_start[-1] + r)
-        self._device, self._segments = {}, {}
+        self._device, self._segments, self._workspace = {}, {}, {}
 
     def on(self, device):
         """(table int32 [B, T, 2], occ_start, occ (at least one element), and for the op chain the int64 index vectors
@@ -76,6 +81,25 @@ class PromptTable:
                 raise RuntimeError("prompt.substitute: a pool entry moved; run once outside the capture first")
             held = self._segments[dev] = (key, torch.tensor([[ptr, r] for ptr, r in zip(key, self.rows)], dtype=torch.int64).to(dev))
         return held[1]
+
+    def workspace(self, device, nbytes):
+        """``memory_loss``'s forward workspace (ticket word + the blocks' doubles) on ``device``: allocated ZEROED once, outside
+        any capture -- the kernel leaves the ticket at zero again, so neither a later call nor a graph replay clears it.  One
+        workspace serves one stream at a time: an eager call on another stream than the last one first waits for that stream."""
+        device = torch.device(device)
+        held = self._workspace.get(device)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if held is None or held[0].numel() < nbytes:
+            if capturing:
+                raise RuntimeError("prompt.memory_loss: the table has no workspace on %s yet; run once outside the capture first"
+                                   % (device,))
+            held = self._workspace[device] = [torch.zeros(nbytes, dtype=torch.uint8, device=device), None]
+        if not capturing:
+            stream = torch.cuda.current_stream(device)
+            if held[1] is not None and held[1] != stream:
+                stream.wait_stream(held[1])
+            held[1] = stream
+        return held[0]
 
 
 def build_table(names_list, cate_to_token_mask_list, pool_keys: Sequence[str], pool_rows: Sequence[int], T: int) -> PromptTable:
@@ -226,3 +250,82 @@ def substitute(encoded_text, table: PromptTable, pool_params):
     if Switches.native_prompt and not FORCE_REFERENCE and native_supported(encoded_text, table, params):
         return _SubstituteNative.apply(encoded_text, table, *params)
     return substitute_reference(encoded_text, table, params)
+
+
+# ---- the text-memory replay's loss ------------------------------------------------------------------------------------------------
+
+def memory_loss_reference(encoded_text, table_or_masks, pool_params):
+    """The definition of ``loss_prompt_memory``: ``L1Loss(mean)(target, encoded_text)``, where ``target`` is ``encoded_text.clone()``
+    with the rows of every category that has an entry in ``pool_params`` overwritten by the entry.  ``table_or_masks`` is
+    ``(names_list, cate_to_token_mask_list)`` -- then this is the reference's loop itself, image by image and category by category,
+    one boolean-mask write each, with ``pool_params`` a mapping from ``-name-`` keys (the caller hands in the learned classes'
+    entries); an empty surplus mask behind a caption's names is passed over, as ``build_table`` passes it -- or a ``PromptTable``:
+    the same target as one indexed write.  Gradients reach ``encoded_text`` and the entries that require them."""
+    if isinstance(table_or_masks, PromptTable):
+        target = substitute_reference(encoded_text, table_or_masks, pool_params)
+    else:
+        names_list, masks_list = table_or_masks
+        target = encoded_text.clone()
+        for b, masks in enumerate(masks_list):
+            for c in range(min(len(masks), len(names_list[b]))):
+                key = pool_key(names_list[b][c])
+                if key in pool_params:
+                    target[b, :masks.shape[1], :][masks[c]] = pool_params[key].to(target.dtype)
+    return torch.nn.functional.l1_loss(target, encoded_text)
+
+
+class _MemoryLossNative(Function):
+    """(x [B, T, D], table, *pool entries) -> the scalar loss through zira_pmem_loss_{fwd,bwd}_f32."""
+
+    @staticmethod
+    def forward(ctx, x, table, *params):
+        lib = _lib.load()
+        x = x.contiguous()
+        B, T, D = x.shape
+        dev = x.device
+        seg_row = table.on(dev)[0]
+        segments = table.segments(params)
+        ws = table.workspace(dev, lib.zira_pmem_workspace_bytes(B, T))
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _check(lib.zira_pmem_loss_fwd_f32(x.data_ptr(), seg_row.data_ptr(), segments.data_ptr(), B, T, D, len(params),
+                                              loss.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                   "zira_pmem_loss_fwd_f32")
+        ctx.save_for_backward(x, *params)
+        ctx.table = table
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        lib = _lib.load()
+        table = ctx.table
+        x, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        B, T, D = x.shape
+        dev = x.device
+        g = grad_loss.contiguous().to(torch.float32)
+        seg_row, occ_start, occ, _, _, _ = table.on(dev)
+        need_pool = any(ctx.needs_input_grad[2:])
+        g_pool = torch.empty((table.n_rows, D), dtype=torch.float32, device=dev) if need_pool else None
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        with torch.cuda.device(dev):
+            _check(lib.zira_pmem_loss_bwd_f32(g.data_ptr(), x.data_ptr(), seg_row.data_ptr(), table.segments(params).data_ptr(),
+                                              occ_start.data_ptr(), occ.data_ptr(), B, T, D, len(params), table.n_rows, table.n_occ,
+                                              g_pool.data_ptr() if need_pool else None, gx.data_ptr() if gx is not None else None,
+                                              torch.cuda.current_stream(dev).cuda_stream),
+                   "zira_pmem_loss_bwd_f32")
+        starts = table.row_start
+        grads = tuple(g_pool[starts[s]:starts[s + 1]] if ctx.needs_input_grad[2 + s] else None for s in range(len(table.keys)))
+        return (gx, None) + grads
+
+
+def memory_loss(encoded_text, table: PromptTable, pool_params):
+    """``loss_prompt_memory`` of ``encoded_text`` [B, T, D] against the pool entries ``table`` names: one autograd node over the HIP
+    kernels where they serve (fp32 CUDA tensors outside autocast, inside the header's limits), ``memory_loss_reference``
+    elsewhere."""
+    from .transformer import Switches
+
+    params = _pool_list(table.keys, pool_params)
+    if Switches.native_prompt_memory and not FORCE_REFERENCE and native_supported(encoded_text, table, params):
+        return _MemoryLossNative.apply(encoded_text, table, *params)
+    return memory_loss_reference(encoded_text, table, params)

@@ -28,7 +28,7 @@ import torch
 import torch.distributed as dist
 
 from . import ema
-from .train import ZiraTrainer
+from .train import MemoryReplayer, ZiraTrainer
 
 
 def clean_state_dict(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -60,6 +60,7 @@ class TaskSpec:
     model_ema: Optional[dict] = None                         # train.model_ema: None = off, or dict(decay=0.999, device="")
     use_ema_weights_for_eval_only: bool = False              # (:338, :534) evaluate a finished task under the averaged weights
     log_period: Optional[int] = None                         # train.log_period (20): <output_dir>/metrics.json every so many iterations; None = off
+    replay: bool = False                                     # --replay (:496-506): a text-only stage of model.replay_memory() iterations; ``data`` is not read
 
     def multiplier(self) -> Callable[[int], float]:
         return self.lr_multiplier or multistep_lr_multiplier((self.max_iter * 4) // 10)
@@ -150,7 +151,13 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
     ``(model, spec) -> dict`` run on the merged model (``do_test`` after training, train_multidatasets.py:338-364, e.g.
     ``evaluation.inference_on_dataset`` over the task's test set); the return value is then ``(path, its result)``.  With
     ``spec.model_ema`` it runs a second time under the averaged weights (``apply_model_ema_and_restore``, :356-364) and that
-    result is the first one's ``"ema"`` entry (the reference's ``ret.update(ema_ret)`` overwrites the plain figures instead)."""
+    result is the first one's ``"ema"`` entry (the reference's ``ret.update(ema_ret)`` overwrites the plain figures instead).
+
+    A replay spec (``spec.replay``, the reference's ``--replay`` stage behind the last task) builds no loader and learns no class:
+    ``max_iter`` iterations of ``MemoryReplayer`` (``model.replay_memory()`` + the trainer's tail), then ``model.after_train()``
+    -- the merge -- and ``model_final.pth``.  The reference's ``MemoryReplayer.after_train`` runs hooks only and saves unmerged
+    branches; merging keeps this chain's invariant that every ``model_final.pth`` starts the next task from merged twins.  No
+    ``add_cls_prompt`` there."""
     final = os.path.join(spec.output_dir, "model_final.pth")
     if resume and os.path.exists(final):
         if evaluate is None:
@@ -164,7 +171,7 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
                 model.ema_state.to(device)
         return final, _evaluate(evaluate, model, spec)
     model = load_model(build_model, init_checkpoint, device)
-    if getattr(model, "use_prompt_tuning", False):
+    if getattr(model, "use_prompt_tuning", False) and not spec.replay:
         # prompt tuning trains the pool entries of this task's classes: they exist before the trainer builds its gradient bucket
         # and optimizer over the trainable tensors (the reference's do_train, train_multidatasets.py:393-394)
         model.add_cls_prompt(list(spec.categories_names))
@@ -173,21 +180,22 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
         from . import metrics
 
         writers = [metrics.CommonMetricPrinter(spec.max_iter), metrics.JSONWriter(os.path.join(spec.output_dir, "metrics.json"))]
-    trainer = ZiraTrainer(model, lr=spec.lr, weight_decay=spec.weight_decay, clip_max_norm=spec.clip_max_norm,
-                          clip_norm_type=spec.clip_norm_type, process_group=process_group,
-                          batch_size_scale=spec.batch_size_scale, model_ema=spec.model_ema,
-                          metrics=None if spec.log_period is None else dict(period=spec.log_period, writers=writers))
+    trainer_class = MemoryReplayer if spec.replay else ZiraTrainer
+    trainer = trainer_class(model, lr=spec.lr, weight_decay=spec.weight_decay, clip_max_norm=spec.clip_max_norm,
+                            clip_norm_type=spec.clip_norm_type, process_group=process_group,
+                            batch_size_scale=spec.batch_size_scale, model_ema=spec.model_ema,
+                            metrics=None if spec.log_period is None else dict(period=spec.log_period, writers=writers))
     base_lrs = [g["lr"] for g in trainer.optimizer.param_groups]   # before a resume: a checkpoint stores the
     start_iter = _resume(spec, model, trainer) if resume else 0    # MULTIPLIED rates of the iteration it was taken at
     trainer.iter = start_iter             # (the reference's step rule, iter % batch_size_scale == 0, counts from here)
     assert len(base_lrs) == len(trainer.optimizer.param_groups)
     multiplier = spec.multiplier()
     period = spec.checkpoint_period or spec.max_iter
-    batches = iter(spec.data(start_iter))
+    batches = None if spec.replay else iter(spec.data(start_iter))
     for it in range(start_iter, spec.max_iter):
         for g, base in zip(trainer.optimizer.param_groups, base_lrs):
             g["lr"] = base * multiplier(it)
-        loss_dict = trainer.run_step(next(batches))
+        loss_dict = trainer.run_step() if spec.replay else trainer.run_step(next(batches))
         if on_step is not None:
             on_step(spec, it, loss_dict)
         if (it + 1) % period == 0:
@@ -197,7 +205,7 @@ def run_task(spec: TaskSpec, build_model, init_checkpoint: Optional[str], device
     for writer in writers:
         writer.close()
     _check_matching(model, process_group)                # ... and before the side branches are merged into the weights
-    trainer.after_train(list(spec.categories_names))
+    trainer.after_train([] if spec.replay else list(spec.categories_names))      # (replay learns no class: the merge only)
     if _is_main(process_group):
         save_checkpoint(spec.output_dir, "model_final", model, trainer, spec.max_iter)
     _barrier(process_group)               # every rank loads this file at the start of the next task

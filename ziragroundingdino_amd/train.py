@@ -96,7 +96,7 @@ class ZiraTrainer:
         bucket and optimizer would no longer train."""
         model, lr, weight_decay, betas = self.model, self._lr, self._wd, self._betas
         model.before_train()  # freeze everything but the side branches
-        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        named = self._trained([(n, p) for n, p in model.named_parameters() if p.requires_grad])
         self.names = [n for n, _ in named]
         self.params = [p for _, p in named]
         # one flat gradient bucket; .grad of every trainable tensor is a view into it
@@ -129,6 +129,10 @@ class ZiraTrainer:
                                                         betas=betas, eps=self.optimizer.defaults["eps"],
                                                         weight_decay=weight_decay,
                                                         amp=self.native_amp_tail and self.amp_dtype is torch.float16)
+
+    def _trained(self, named):
+        """The (name, parameter) pairs the bucket and the optimizer are built over: every trainable tensor."""
+        return named
 
     fused_optimizer = True   # class-level switch (tests compare with the multi-tensor implementation)
     # class-level switch: norm + clip + AdamW + gradient clear as two native launches (csrc/optim_tail.hip) instead of the op
@@ -238,6 +242,11 @@ class ZiraTrainer:
                 tr.__dict__["after_encoder"] = None   # hook must not stay armed, holding the next minibatch)
         if can_prefetch and self._prefetched is None:
             self._prefetched = self.model.prefetch_frontend(next_data)
+        return self._backward_and_step(loss_dict)
+
+    def _backward_and_step(self, loss_dict) -> Dict[str, torch.Tensor]:
+        """The tail of an iteration, shared by ``run_step`` and ``MemoryReplayer.run_step``: backward of the loss dict's sum,
+        the all-reduce, clip / AdamW or the native tails, the EMA and the metrics; returns the detached loss dict."""
         losses = getattr(loss_dict, "total", None)   # the model's own sum of the same terms (criterion.LossDict)
         if losses is None:
             losses = sum(loss_dict.values())
@@ -333,6 +342,36 @@ class ZiraTrainer:
             # the prompt-pool entries created above have no average yet: they start from the model (the reference's
             # ``apply_to`` would assert on them in the evaluation that follows)
             self._ema_updater.state.adopt_missing(self._ema_model)
+
+
+class MemoryReplayer(ZiraTrainer):
+    """The text-only replay stage behind the last task (reference ``MemoryReplayer``, train_multidatasets.py:257-317, ``--replay``
+    :496-506): an iteration is ``model.replay_memory()`` -- no images, no data loader -- then backward and the same tail as
+    ``ZiraTrainer.run_step``, with ``data_time = 0`` in the metrics.
+
+    The bucket and the optimizer hold the text side only (``model.replay_parameter_prefixes()``): the vision side branches and
+    their twins get no gradient in replay, and in the reference their ``grad`` is None, so the optimizer skips them -- inside
+    the bucket they would be weight-decayed and their moments updated with zero gradients."""
+
+    def _trained(self, named):
+        prefixes = tuple(self.model.replay_parameter_prefixes())
+        kept = [(n, p) for n, p in named if n.startswith(prefixes)]
+        if not kept:
+            raise RuntimeError("[MemoryReplayer] no trainable text-side parameter (%s)" % ", ".join(prefixes))
+        return kept
+
+    def run_step(self, data=None, next_data=None) -> Dict[str, torch.Tensor]:
+        assert self.model.training, "[MemoryReplayer] model was changed to eval mode!"
+        self._check_bucket()
+        if self._ema_updater is not None and not self._ema_started:
+            self.ema_before_train()
+        self.data_time = 0.0
+        if self.amp_dtype is not None:
+            with torch.autocast(self.flat_grad.device.type, dtype=self.amp_dtype):
+                loss_dict = self.model.replay_memory()
+        else:
+            loss_dict = self.model.replay_memory()
+        return self._backward_and_step(loss_dict)
 
 
 def synthetic_batch(batch_size, height=800, width=1333, n_categories=7, boxes_per_image=5, seed=0,
