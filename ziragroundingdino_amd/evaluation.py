@@ -6,6 +6,8 @@ The hot part of COCOeval is ``evaluateImg``: per (image, category, area range, I
 of up to 100 detections against the image's ground truth.  ``match`` runs it for a whole batch in one launch where the
 detections already are (csrc/apmatch.hip, the rules stated at ``zira_ap_match`` in include/zira_msda.h); ``match_reference`` is
 the same function in numpy fp64 on any device, for what ``match_supported`` declines, for CPU tensors and for the tests.
+The padding of a batch, the score order, the kept state's read-back, the greedy walk of ``match_reference`` and the dataset
+loop are ``box_eval``'s, shared with the LVIS, VOC and phrase evaluators; this module holds what is COCO's own.
 ``CocoBoxEvaluator`` keeps the per-batch results on the device until ``evaluate()``, which is pycocotools' ``accumulate`` +
 ``summarize``: ``accumulate_device`` fills the precision / recall tables where the state is (csrc/apaccum.hip, one launch, the
 rules stated at ``zira_ap_accumulate``) and only the tables are read back; ``accumulate`` is the same function in numpy fp64 on
@@ -16,11 +18,12 @@ round trip through pycocotools is the input: tensors instead of files.
 ``matched`` / ``ignored`` are int64 tensors that hold the 64 bits of the entry's u64 words (bit ``a * T + t``).
 """
 import ctypes
+import sys
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, box_eval
 
 MAX_B, MAX_K, MAX_G, MAX_BITS = 65535, 1024, 1024, 64
 MAX_THRS, MAX_AREAS = _lib.AP_MAX_THRS, _lib.AP_MAX_AREAS
@@ -78,16 +81,8 @@ def match(scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_crowd, n_
     thrs, rngs, max_det = _params(iou_thrs, area_rngs, max_det)
     (B, K), G, T, A = scores.shape, gt_label.shape[1], len(thrs), len(rngs)
     lib = _lib.load()
-    dev = scores.device
-    rank = torch.empty((B, K), dtype=torch.int32, device=dev)
-    matched = torch.empty((B, K), dtype=torch.int64, device=dev)
-    ignored = torch.empty((B, K), dtype=torch.int64, device=dev)
-    gt_ignored = torch.empty((B, G), dtype=torch.uint8, device=dev)
-    gt_of = torch.empty((B, K, A * T), dtype=torch.int32, device=dev) if with_gt_of else None
-    c_thrs = (ctypes.c_double * T)(*thrs)
-    c_rngs = (ctypes.c_double * (2 * A))(*[v for r in rngs for v in r])
-    ptr = lambda t: t.data_ptr() if G > 0 else None
-    with torch.cuda.device(dev):
+    (rank, matched, ignored, gt_ignored, gt_of), c_thrs, c_rngs, ptr = box_eval.match_launch(scores, G, thrs, rngs, with_gt_of)
+    with torch.cuda.device(scores.device):
         rc = lib.zira_ap_match(scores.data_ptr(), labels.data_ptr(), xyxy.data_ptr(), n_keep.data_ptr(), B, K, ptr(gt_xywh),
                                ptr(gt_area), ptr(gt_label), ptr(gt_crowd), ptr(n_gt), G, c_thrs, T, c_rngs, A, max_det,
                                rank.data_ptr(), matched.data_ptr(), ignored.data_ptr(), ptr(gt_ignored),
@@ -99,9 +94,9 @@ def match(scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_crowd, n_
 
 def match_reference(scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_crowd, n_gt, iou_thrs=DEFAULT_IOU_THRS,
                     area_rngs=DEFAULT_AREA_RNGS, max_det=100, with_gt_of=True):
-    """What ``match`` returns, computed on the host in numpy fp64 (tensors on any device; the results go back to it).  Per image
-    the IoU matrix and the ignore flags are formed at once; the walk over the detections is the only loop, with all A T
-    problems and all GTs of a step side by side."""
+    """What ``match`` returns, computed on the host in numpy fp64 (tensors on any device; the results go back to it): per image
+    ``box_eval.match_image`` under COCO's rules -- a crowd GT may be taken again and its union is the detection's area -- for
+    the detections inside the per-class ``max_det``."""
     dets, gts = (scores, labels, xyxy, n_keep), (gt_xywh, gt_area, gt_label, gt_crowd, n_gt)
     if not _shapes_ok(dets, gts):
         raise ValueError("match_reference: scores / labels [B, K], xyxy [B, K, 4], n_keep [B], gt_xywh [B, G, 4], "
@@ -110,67 +105,17 @@ def match_reference(scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt
     (B, K), G, T, A = scores.shape, gt_label.shape[1], len(thrs), len(rngs)
     if not 1 <= max_det or A * T > MAX_BITS or A < 1 or T < 1:
         raise ValueError("match_reference: max_det >= 1, 1 <= A T <= 64")
-    dev = scores.device
-    host = lambda t, dt: t.detach().cpu().numpy().astype(dt, copy=False)
-    lab, box, nk_all = host(labels, np.int64), host(xyxy, np.float32), np.clip(host(n_keep, np.int64), 0, K)
-    gbox, garea, glab = host(gt_xywh, np.float64), host(gt_area, np.float64), host(gt_label, np.int64)
-    gcrowd, ng_all = host(gt_crowd, np.uint8) != 0, np.clip(host(n_gt, np.int64), 0, G)
-    AT = A * T
-    lo = np.array([r[0] for r in rngs])[:, None]
-    hi = np.array([r[1] for r in rngs])[:, None]
-    floor = np.repeat(np.minimum(np.array(thrs), 1 - 1e-10)[None, :], A, 0).reshape(AT, 1)     # problem a T + t
-    weight = (np.uint64(1) << np.arange(AT, dtype=np.uint64))
-
-    rank = np.full((B, K), -1, np.int32)
-    matched = np.zeros((B, K), np.uint64)
-    ignored = np.zeros((B, K), np.uint64)
-    gt_ign = np.zeros((B, G), np.uint8)
-    gt_of = np.full((B, K, AT), -1, np.int32)
+    lab, box, nk_all, gbox, garea, glab, gcrowd, ng_all = box_eval.reference_inputs(*dets[1:], *gts)
+    constants = box_eval.reference_constants(thrs, rngs)
+    rank, matched, ignored, gt_ign, gt_of = box_eval.reference_outputs(B, K, G, A * T)
     for b in range(B):
         nk, ng = int(nk_all[b]), int(ng_all[b])
         l = lab[b, :nk]
         rank[b, :nk] = (np.tril(l[:, None] == l[None, :], -1)).sum(1)
-        crowd = gcrowd[b, :ng]
-        ign_a = crowd[None, :] | (garea[b, :ng][None, :] < lo) | (garea[b, :ng][None, :] > hi)                 # [A, ng]
-        gt_ign[b, :ng] = (ign_a.astype(np.uint8) << np.arange(A, dtype=np.uint8)[:, None]).sum(0, dtype=np.uint8)
-        # IoU [nk, ng], every operation on its own
-        dx, dy = box[b, :nk, 0].astype(np.float64), box[b, :nk, 1].astype(np.float64)
-        dw = (box[b, :nk, 2] - box[b, :nk, 0]).astype(np.float64)
-        dh = (box[b, :nk, 3] - box[b, :nk, 1]).astype(np.float64)
-        da = dw * dh
-        gx, gy, gw, gh = (gbox[b, :ng, i] for i in range(4))
-        ga = gw * gh
-        w = np.minimum((dx + dw)[:, None], (gx + gw)[None, :]) - np.maximum(dx[:, None], gx[None, :])
-        h = np.minimum((dy + dh)[:, None], (gy + gh)[None, :]) - np.maximum(dy[:, None], gy[None, :])
-        inter = w * h
-        union = np.where(crowd[None, :], da[:, None], da[:, None] + ga[None, :] - inter)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            iou = np.where((w > 0) & (h > 0), inter / union, 0.0)
-        same = l[:, None] == glab[b, :ng][None, :]
-        ign = np.repeat(ign_a, T, 0)                         # [AT, ng]
-        det_out = np.repeat((da[None, :] < lo) | (da[None, :] > hi), T, 0)   # [AT, nk]: an unmatched detection's flag
-        taken = np.zeros((AT, ng), bool)
-        rows = np.arange(AT)
-        for k in range(nk):
-            if rank[b, k] >= max_det:
-                continue
-            m_bits, i_bits = np.zeros(AT, bool), det_out[:, k].copy()
-            if ng and same[k].any():
-                cand = same[k][None, :] & (crowd[None, :] | ~taken) & ~(iou[k][None, :] < floor)
-                first = cand & ~ign
-                pool = np.where(first.any(1)[:, None], first, cand)      # the not-ignored GTs shut the ignored ones out
-                val = np.where(pool, iou[k][None, :], -np.inf)
-                top = val.max(1)
-                pick = ng - 1 - np.argmax((pool & (val == top[:, None]))[:, ::-1], 1)       # the LAST of the best
-                got = pool.any(1)
-                gt_of[b, k, got] = pick[got]
-                taken[rows[got], pick[got]] = True
-                m_bits = got
-                i_bits = np.where(got, ign[rows, pick], i_bits)
-            matched[b, k] = weight[m_bits].sum(dtype=np.uint64)
-            ignored[b, k] = weight[i_bits].sum(dtype=np.uint64)
-    t = lambda a: torch.from_numpy(a).to(dev)
-    return (t(rank), t(matched.view(np.int64)), t(ignored.view(np.int64)), t(gt_ign), t(gt_of) if with_gt_of else None)
+        matched[b, :nk], ignored[b, :nk], gt_of[b, :nk], gt_ign[b, :ng] = box_eval.match_image(      # the per-class max_det cut
+            l, rank[b, :nk] < max_det, box[b, :nk], gbox[b, :ng], garea[b, :ng], glab[b, :ng], gcrowd[b, :ng], constants,
+            crowd_rules=True)
+    return box_eval.reference_result(scores.device, rank, matched, ignored, gt_ign, gt_of, with_gt_of)
 
 
 def accumulate(scores, labels, rank, matched, ignored, gt_label, gt_ignored, num_classes, iou_thrs, area_rngs, max_dets,
@@ -314,12 +259,13 @@ def summarize(precision, recall, class_names, iou_thrs, max_dets):
     return out
 
 
-class CocoBoxEvaluator:
+class CocoBoxEvaluator(box_eval.BoxEvaluator):
     """detectron2's ``DatasetEvaluator`` surface (``reset`` / ``process`` / ``evaluate``) for COCO box AP.  ``process`` pads the
     batch, matches it in one launch and keeps the result where it is; nothing is read back before ``evaluate()``, which
     accumulates where the state is (``accumulate_device``) and reads back the two tables, or -- CPU state, state on several
     devices after ``merge``, parameters outside the entry's limits, ``FORCE_REFERENCE`` -- reads back the state and accumulates
     on the host.  The tables are the same bits either way."""
+    _STATE, _WORDS, _WORD_DTYPE = _STATE, ("matched", "ignored"), np.uint64
 
     def __init__(self, class_names, max_dets=(1, 10, 100), iou_thrs=None, area_rngs=None):
         self.class_names = list(class_names)
@@ -328,55 +274,22 @@ class CocoBoxEvaluator:
         self.area_rngs = tuple((float(lo), float(hi)) for lo, hi in (DEFAULT_AREA_RNGS if area_rngs is None else area_rngs))
         self.reset()
 
-    def reset(self):
-        self._batches = []
-
     def process_padded(self, scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_crowd, n_gt):
         """One batch from raw tensors (``match``'s inputs; rows need not be sorted: a stable sort puts them in score order)."""
-        B, K = scores.shape
-        G = gt_label.shape[1]
-        dev = scores.device
-        valid = torch.arange(K, device=dev)[None, :] < n_keep[:, None]
-        key = torch.where(valid, scores, torch.full_like(scores, float("-inf")))
-        order = torch.sort(key, dim=1, descending=True, stable=True)[1]
-        scores, labels = torch.gather(scores, 1, order).contiguous(), torch.gather(labels, 1, order).contiguous()
-        xyxy = torch.gather(xyxy, 1, order[:, :, None].expand(B, K, 4)).contiguous()
-        max_det = min(self.max_dets[-1], K)
-        args = (scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_crowd, n_gt, self.iou_thrs, self.area_rngs, max_det)
-        fn = match if not FORCE_REFERENCE and match_supported(*args) else match_reference
-        rank, matched, ignored, gt_ignored, _ = fn(*args, with_gt_of=False)
-        gt_valid = torch.arange(G, device=dev)[None, :] < n_gt[:, None]
+        scores, labels, xyxy = box_eval.sort_by_score(scores, labels, xyxy, n_keep)
+        max_det = min(self.max_dets[-1], scores.shape[1])
+        rank, matched, ignored, gt_ignored, _ = box_eval.match_batch(
+            sys.modules[__name__], scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_crowd, n_gt, self.iou_thrs,
+            self.area_rngs, max_det)
         self._batches.append(dict(scores=scores, labels=labels, rank=rank, matched=matched, ignored=ignored,
-                                  gt_label=torch.where(gt_valid, gt_label, torch.full_like(gt_label, -1)),
-                                  gt_ignored=gt_ignored))
+                                  gt_label=box_eval.mask_behind(gt_label, n_gt), gt_ignored=gt_ignored))
 
     def process(self, inputs, outputs):
         """``inputs``: the batched_inputs dicts, each with ``"annotations"`` (COCO dicts: ``bbox`` xywh in the output image's
         pixels, ``category_id`` the contiguous index, ``iscrowd``, optionally ``area``); ``outputs``: what the model returns in
         eval mode, ``[{"instances": Instances}]``."""
-        insts = [o["instances"] for o in outputs]
-        dev = insts[0].scores.device
-        B = len(insts)
-        lens = [len(i) for i in insts]
-        K = max(1, max(lens))
-        scores = torch.zeros((B, K), dtype=torch.float32, device=dev)
-        labels = torch.zeros((B, K), dtype=torch.int64, device=dev)
-        xyxy = torch.zeros((B, K, 4), dtype=torch.float32, device=dev)
-        for b, (inst, n) in enumerate(zip(insts, lens)):
-            scores[b, :n], labels[b, :n], xyxy[b, :n] = inst.scores, inst.pred_classes, inst.pred_boxes.tensor
-        annos = [list(x.get("annotations", ())) for x in inputs]
-        G = max(len(a) for a in annos)
-        gt = np.zeros((B, G, 5))
-        gl = np.zeros((B, G), np.int64)
-        gc = np.zeros((B, G), np.uint8)
-        for b, anns in enumerate(annos):
-            for g, ann in enumerate(anns):
-                x, y, w, h = (float(v) for v in ann["bbox"])
-                gt[b, g] = (x, y, w, h, float(ann["area"]) if "area" in ann else w * h)
-                gl[b, g], gc[b, g] = int(ann["category_id"]), int(bool(ann.get("iscrowd", 0)))
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        self.process_padded(scores, labels, xyxy, torch.tensor(lens, dtype=torch.int32).to(dev), up(gt[:, :, :4]),
-                            up(gt[:, :, 4]), up(gl), up(gc), torch.tensor([len(a) for a in annos], dtype=torch.int32).to(dev))
+        dets = box_eval.pad_instances(outputs)
+        self.process_padded(*dets, *box_eval.pad_annotations(inputs, dets[0].device, "iscrowd", with_area=True))
 
     def merge(self, other):
         """Append another evaluator's state (a data-parallel run gathers its ranks' evaluators with this)."""
@@ -385,53 +298,16 @@ class CocoBoxEvaluator:
         self._batches.extend(other._batches)
         return self
 
-    def _gather(self):
-        """Every kept tensor as a host array, through ONE device -> host copy per device that holds state."""
-        host = [None] * len(self._batches)
-        for dev in {b["scores"].device for b in self._batches}:
-            idx = [i for i, b in enumerate(self._batches) if b["scores"].device == dev]
-            flat = [self._batches[i][k].contiguous().view(-1).view(torch.uint8) for i in idx for k in _STATE]
-            blob = torch.cat(flat).cpu().numpy()
-            off = 0
-            for i in idx:
-                host[i] = {}
-                for k in _STATE:
-                    t = self._batches[i][k]
-                    n = t.numel() * t.element_size()
-                    dt = np.uint64 if k in ("matched", "ignored") else torch.empty(0, dtype=t.dtype).numpy().dtype
-                    host[i][k] = np.frombuffer(blob[off:off + n].tobytes(), dtype=dt)
-                    off += n
-        return host
-
     def evaluate(self):
-        C = len(self.class_names)
-        if not FORCE_REFERENCE and accumulate_supported(self._batches, C, self.iou_thrs, self.area_rngs, self.max_dets):
-            p, r = accumulate_device(self._batches, C, self.iou_thrs, self.area_rngs, self.max_dets)
-            both = torch.cat([p.view(-1), r.view(-1)]).cpu().numpy()      # ONE device -> host copy
-            precision, recall = both[:p.numel()].reshape(tuple(p.shape)), both[p.numel():].reshape(tuple(r.shape))
-            self.precision, self.recall = precision, recall
-            return {"bbox": summarize(precision, recall, self.class_names, self.iou_thrs, self.max_dets)}
-        host = self._gather()
-        cat = lambda k, dt: np.concatenate([h[k] for h in host]) if host else np.zeros(0, dt)
-        rank, gt_label = cat("rank", np.int32), cat("gt_label", np.int64)
-        det, gt = rank >= 0, gt_label >= 0
-        precision, recall = accumulate(cat("scores", np.float32)[det].astype(np.float64), cat("labels", np.int64)[det], rank[det],
-                                       cat("matched", np.uint64)[det], cat("ignored", np.uint64)[det], gt_label[gt],
-                                       cat("gt_ignored", np.uint8)[gt], len(self.class_names), self.iou_thrs, self.area_rngs,
-                                       self.max_dets)
+        args = (len(self.class_names), self.iou_thrs, self.area_rngs, self.max_dets)
+        if not FORCE_REFERENCE and accumulate_supported(self._batches, *args):
+            precision, recall = box_eval.read_back(*accumulate_device(self._batches, *args))    # ONE device -> host copy
+        else:
+            precision, recall = accumulate(*box_eval.accumulate_inputs(self._gather()), *args)
         self.precision, self.recall = precision, recall
         return {"bbox": summarize(precision, recall, self.class_names, self.iou_thrs, self.max_dets)}
 
 
 def inference_on_dataset(model, batches, evaluator):
-    """The reference's evaluation loop (train_multidatasets.py:338-364): eval mode, no gradients, ``process`` per batch."""
-    was_training = model.training
-    model.eval()
-    evaluator.reset()
-    try:
-        with torch.no_grad():
-            for inputs in batches:
-                evaluator.process(inputs, model(inputs))
-    finally:
-        model.train(was_training)
-    return evaluator.evaluate()
+    """The reference's evaluation loop (``box_eval.run_dataset``) over ``model(inputs)``."""
+    return box_eval.run_dataset(model, batches, evaluator, lambda inputs: model(inputs))

@@ -14,18 +14,19 @@ of its positive set (those of its ground truth), checked and found empty for its
 (csrc/lvismatch.hip, the rules stated in include/zira_lvis.h); ``match_reference`` is the same function in numpy fp64 on any device,
 for what ``match_supported`` declines, for CPU tensors and for the tests.  Its outputs are laid out as ``evaluation.match``'s, so
 ``LVISBoxEvaluator`` keeps them on the device until ``evaluate()`` and accumulates them with ``evaluation.accumulate_device`` /
-``accumulate`` as they are, ``max_dets = (300,)``; ``summarize`` works on the small tables.
+``accumulate`` as they are, ``max_dets = (300,)``; ``summarize`` works on the small tables.  Padding, score order, read-back and
+the greedy walk itself are ``box_eval``'s: ``match_reference`` here states only the cut, the filter and the not-exhaustive flag.
 
 ``matched`` / ``ignored`` are int64 tensors that hold the 64 bits of the entry's u64 words (bit ``a * T + t``); the category bitsets
 are int32 tensors that hold the 32 bits of the entry's u32 words (category ``c`` at bit ``c % 32`` of word ``c // 32``).
 """
-import ctypes
 import json
+import sys
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, box_eval
 from . import evaluation as ev
 
 MAX_B, MAX_K, MAX_G, MAX_CLASSES = (_lib.LVIS_CONSTANTS[k] for k in ("ZIRA_LVIS_MAX_B", "ZIRA_LVIS_MAX_K", "ZIRA_LVIS_MAX_G",
@@ -76,16 +77,8 @@ def match(scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_ignore, n
     thrs, rngs, max_det = ev._params(iou_thrs, area_rngs, max_det)
     (B, K), G, T, A = scores.shape, gt_label.shape[1], len(thrs), len(rngs)
     lib = _lib.load()
-    dev = scores.device
-    rank = torch.empty((B, K), dtype=torch.int32, device=dev)
-    matched = torch.empty((B, K), dtype=torch.int64, device=dev)
-    ignored = torch.empty((B, K), dtype=torch.int64, device=dev)
-    gt_ignored = torch.empty((B, G), dtype=torch.uint8, device=dev)
-    gt_of = torch.empty((B, K, A * T), dtype=torch.int32, device=dev) if with_gt_of else None
-    c_thrs = (ctypes.c_double * T)(*thrs)
-    c_rngs = (ctypes.c_double * (2 * A))(*[v for r in rngs for v in r])
-    ptr = lambda t: t.data_ptr() if G > 0 else None
-    with torch.cuda.device(dev):
+    (rank, matched, ignored, gt_ignored, gt_of), c_thrs, c_rngs, ptr = box_eval.match_launch(scores, G, thrs, rngs, with_gt_of)
+    with torch.cuda.device(scores.device):
         rc = lib.zira_lvis_match(scores.data_ptr(), labels.data_ptr(), xyxy.data_ptr(), n_keep.data_ptr(), B, K, ptr(gt_xywh),
                                  ptr(gt_area), ptr(gt_label), ptr(gt_ignore), ptr(n_gt), G, neg_set.data_ptr(), nel_set.data_ptr(),
                                  int(num_classes), c_thrs, T, c_rngs, A, max_det, rank.data_ptr(), matched.data_ptr(),
@@ -99,8 +92,8 @@ def match(scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_ignore, n
 def match_reference(scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_ignore, n_gt, neg_set, nel_set, num_classes,
                     iou_thrs=DEFAULT_IOU_THRS, area_rngs=DEFAULT_AREA_RNGS, max_det=DEFAULT_MAX_DETS, with_gt_of=True):
     """What ``match`` returns, computed on the host in numpy fp64 (tensors on any device; the results go back to it): the
-    definition.  Per image the cut, the category filter, the IoU matrix and the ignore flags are formed at once; the walk over
-    the detections is the only loop, with all A T problems and all GTs of a step side by side."""
+    definition.  Per image the cut and the category filter, then ``box_eval.match_image`` under LVIS's rules -- a taken GT stays
+    taken, flagged or not, and an unmatched detection of a not-exhaustively annotated category is ignored."""
     t = (scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_ignore, n_gt, neg_set, nel_set)
     if not _shapes_ok(t, num_classes):
         raise ValueError("match_reference: scores / labels [B, K], xyxy [B, K, 4], n_keep [B], gt_xywh [B, G, 4], gt_area / "
@@ -109,24 +102,11 @@ def match_reference(scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt
     (B, K), G, T, A, C = scores.shape, gt_label.shape[1], len(thrs), len(rngs), int(num_classes)
     if not 1 <= max_det or A * T > MAX_BITS or A < 1 or T < 1:
         raise ValueError("match_reference: max_det >= 1, 1 <= A T <= 64")
-    dev = scores.device
-    host = lambda x, dt: x.detach().cpu().numpy().astype(dt, copy=False)
-    lab, box, nk_all = host(labels, np.int64), host(xyxy, np.float32), np.clip(host(n_keep, np.int64), 0, K)
-    gbox, garea, glab = host(gt_xywh, np.float64), host(gt_area, np.float64), host(gt_label, np.int64)
-    gflag, ng_all = host(gt_ignore, np.uint8) != 0, np.clip(host(n_gt, np.int64), 0, G)
-    neg, nel = host(neg_set, np.int32).view(np.uint32), host(nel_set, np.int32).view(np.uint32)
-    AT = A * T
-    lo = np.array([r[0] for r in rngs])[:, None]
-    hi = np.array([r[1] for r in rngs])[:, None]
-    floor = np.repeat(np.minimum(np.array(thrs), 1 - 1e-10)[None, :], A, 0).reshape(AT, 1)     # problem a T + t
-    weight = (np.uint64(1) << np.arange(AT, dtype=np.uint64))
+    lab, box, nk_all, gbox, garea, glab, gflag, ng_all = box_eval.reference_inputs(*t[1:9])
+    neg, nel = (x.detach().cpu().numpy().astype(np.int32, copy=False).view(np.uint32) for x in (neg_set, nel_set))
+    constants = box_eval.reference_constants(thrs, rngs)
     in_set = lambda words, c: ((words[c >> 5] >> (c & 31).astype(np.uint32)) & np.uint32(1)) != 0
-
-    rank = np.full((B, K), -1, np.int32)
-    matched = np.zeros((B, K), np.uint64)
-    ignored = np.zeros((B, K), np.uint64)
-    gt_ign = np.zeros((B, G), np.uint8)
-    gt_of = np.full((B, K, AT), -1, np.int32)
+    rank, matched, ignored, gt_ign, gt_of = box_eval.reference_outputs(B, K, G, A * T)
     for b in range(B):
         nk, ng = min(int(nk_all[b]), max_det), int(ng_all[b])                       # the image cut
         gl = glab[b, :ng]
@@ -134,48 +114,12 @@ def match_reference(scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt
         in_c = (l >= 0) & (l < C)
         c = np.where(in_c, l, 0)
         takes = in_c & (np.isin(l, gl) | in_set(neg[b], c))                         # the category filter
-        not_exhaustive = in_c & in_set(nel[b], c)
         l = np.where(takes, l, -1)
         rank[b, :nk] = np.where(takes, (np.tril(l[:, None] == l[None, :], -1)).sum(1), -1)
-        ign_a = gflag[b, :ng][None, :] | (garea[b, :ng][None, :] < lo) | (garea[b, :ng][None, :] > hi)          # [A, ng]
-        gt_ign[b, :ng] = (ign_a.astype(np.uint8) << np.arange(A, dtype=np.uint8)[:, None]).sum(0, dtype=np.uint8)
-        # IoU [nk, ng], every operation on its own
-        dx, dy = box[b, :nk, 0].astype(np.float64), box[b, :nk, 1].astype(np.float64)
-        dw = (box[b, :nk, 2] - box[b, :nk, 0]).astype(np.float64)
-        dh = (box[b, :nk, 3] - box[b, :nk, 1]).astype(np.float64)
-        da = dw * dh
-        gx, gy, gw, gh = (gbox[b, :ng, i] for i in range(4))
-        ga = gw * gh
-        w = np.minimum((dx + dw)[:, None], (gx + gw)[None, :]) - np.maximum(dx[:, None], gx[None, :])
-        h = np.minimum((dy + dh)[:, None], (gy + gh)[None, :]) - np.maximum(dy[:, None], gy[None, :])
-        inter = w * h
-        with np.errstate(divide="ignore", invalid="ignore"):
-            iou = np.where((w > 0) & (h > 0), inter / (da[:, None] + ga[None, :] - inter), 0.0)
-        same = (l[:, None] == gl[None, :]) & takes[:, None]
-        ign = np.repeat(ign_a, T, 0)                         # [AT, ng]
-        det_out = np.repeat((da[None, :] < lo) | (da[None, :] > hi), T, 0) | not_exhaustive[None, :]   # an unmatched detection's flag
-        taken = np.zeros((AT, ng), bool)
-        rows = np.arange(AT)
-        for k in range(nk):
-            if not takes[k]:
-                continue
-            m_bits, i_bits = np.zeros(AT, bool), det_out[:, k].copy()
-            if ng and same[k].any():
-                cand = same[k][None, :] & ~taken & ~(iou[k][None, :] < floor)
-                first = cand & ~ign
-                pool = np.where(first.any(1)[:, None], first, cand)      # the not-ignored GTs shut the ignored ones out
-                val = np.where(pool, iou[k][None, :], -np.inf)
-                top = val.max(1)
-                pick = ng - 1 - np.argmax((pool & (val == top[:, None]))[:, ::-1], 1)       # the LAST of the best
-                got = pool.any(1)
-                gt_of[b, k, got] = pick[got]
-                taken[rows[got], pick[got]] = True
-                m_bits = got
-                i_bits = np.where(got, ign[rows, pick], i_bits)
-            matched[b, k] = weight[m_bits].sum(dtype=np.uint64)
-            ignored[b, k] = weight[i_bits].sum(dtype=np.uint64)
-    t = lambda a: torch.from_numpy(a).to(dev)
-    return (t(rank), t(matched.view(np.int64)), t(ignored.view(np.int64)), t(gt_ign), t(gt_of) if with_gt_of else None)
+        matched[b, :nk], ignored[b, :nk], gt_of[b, :nk], gt_ign[b, :ng] = box_eval.match_image(
+            l, takes, box[b, :nk], gbox[b, :ng], garea[b, :ng], gl, gflag[b, :ng], constants, crowd_rules=False,
+            unmatched_ignored=in_c & in_set(nel[b], c))                             # not exhaustively annotated
+    return box_eval.reference_result(scores.device, rank, matched, ignored, gt_ign, gt_of, with_gt_of)
 
 
 def category_bitsets(lists, C, device="cpu"):
@@ -234,12 +178,13 @@ def summarize(precision, recall, frequencies, iou_thrs, max_det=DEFAULT_MAX_DETS
     return out
 
 
-class LVISBoxEvaluator:
+class LVISBoxEvaluator(box_eval.BoxEvaluator):
     """detectron2's ``DatasetEvaluator`` surface (``reset`` / ``process`` / ``evaluate``) for LVIS box AP, with
     ``CocoBoxEvaluator``'s division of work: ``process`` pads the batch, matches it in one launch and keeps the result where it
     is; nothing is read back before ``evaluate()``, which accumulates where the state is (``evaluation.accumulate_device``) and
     reads back the two tables, or -- CPU state, state on several devices after ``merge``, parameters outside the entry's limits,
     ``FORCE_REFERENCE`` -- reads back the state and accumulates on the host.  The tables are the same bits either way."""
+    _STATE, _WORDS, _WORD_DTYPE = ev._STATE, ("matched", "ignored"), np.uint64       # ``evaluation.match``'s layout
 
     def __init__(self, class_names, frequencies, max_dets=DEFAULT_MAX_DETS, iou_thrs=None, area_rngs=None):
         self.class_names = list(class_names)
@@ -251,57 +196,25 @@ class LVISBoxEvaluator:
         self.area_rngs = tuple((float(lo), float(hi)) for lo, hi in (DEFAULT_AREA_RNGS if area_rngs is None else area_rngs))
         self.reset()
 
-    def reset(self):
-        self._batches = []
-
     def process_padded(self, scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_ignore, n_gt, neg_set, nel_set):
         """One batch from raw tensors (``match``'s inputs; rows need not be sorted: a stable sort puts them in score order)."""
-        B, K = scores.shape
-        G = gt_label.shape[1]
-        dev = scores.device
-        valid = torch.arange(K, device=dev)[None, :] < n_keep[:, None]
-        key = torch.where(valid, scores, torch.full_like(scores, float("-inf")))
-        order = torch.sort(key, dim=1, descending=True, stable=True)[1]
-        scores, labels = torch.gather(scores, 1, order).contiguous(), torch.gather(labels, 1, order).contiguous()
-        xyxy = torch.gather(xyxy, 1, order[:, :, None].expand(B, K, 4)).contiguous()
-        args = (scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_ignore, n_gt, neg_set, nel_set, len(self.class_names),
-                self.iou_thrs, self.area_rngs, min(self.max_dets, K))
-        fn = match if not FORCE_REFERENCE and match_supported(*args) else match_reference
-        rank, matched, ignored, gt_ignored, _ = fn(*args, with_gt_of=False)
-        gt_valid = torch.arange(G, device=dev)[None, :] < n_gt[:, None]
+        scores, labels, xyxy = box_eval.sort_by_score(scores, labels, xyxy, n_keep)
+        K = scores.shape[1]
+        rank, matched, ignored, gt_ignored, _ = box_eval.match_batch(
+            sys.modules[__name__], scores, labels, xyxy, n_keep, gt_xywh, gt_area, gt_label, gt_ignore, n_gt, neg_set, nel_set,
+            len(self.class_names), self.iou_thrs, self.area_rngs, min(self.max_dets, K))
         self._batches.append(dict(scores=scores, labels=labels, rank=rank, matched=matched, ignored=ignored,
-                                  gt_label=torch.where(gt_valid, gt_label, torch.full_like(gt_label, -1)),
-                                  gt_ignored=gt_ignored, n_pred=n_keep.clamp(0, K).sum(dtype=torch.int64)))
+                                  gt_label=box_eval.mask_behind(gt_label, n_gt), gt_ignored=gt_ignored,
+                                  n_pred=n_keep.clamp(0, K).sum(dtype=torch.int64)))
 
     def process(self, inputs, outputs):
         """``inputs``: the batched_inputs dicts, each with ``"annotations"`` (dicts: ``bbox`` xywh in the output image's pixels,
         ``category_id`` the contiguous index, optionally ``area`` and ``ignore``), ``"neg_category_ids"`` and
         ``"not_exhaustive_category_ids"`` (contiguous 0-based ids, i.e. after the metadata's mapping; a missing key is an empty
         list); ``outputs``: what the model returns in eval mode, ``[{"instances": Instances}]``."""
-        insts = [o["instances"] for o in outputs]
-        dev = insts[0].scores.device
-        B = len(insts)
-        lens = [len(i) for i in insts]
-        K = max(1, max(lens))
-        C = len(self.class_names)
-        scores = torch.zeros((B, K), dtype=torch.float32, device=dev)
-        labels = torch.zeros((B, K), dtype=torch.int64, device=dev)
-        xyxy = torch.zeros((B, K, 4), dtype=torch.float32, device=dev)
-        for b, (inst, n) in enumerate(zip(insts, lens)):
-            scores[b, :n], labels[b, :n], xyxy[b, :n] = inst.scores, inst.pred_classes, inst.pred_boxes.tensor
-        annos = [list(x.get("annotations", ())) for x in inputs]
-        G = max(len(a) for a in annos)
-        gt = np.zeros((B, G, 5))
-        gl = np.zeros((B, G), np.int64)
-        gi = np.zeros((B, G), np.uint8)
-        for b, anns in enumerate(annos):
-            for g, ann in enumerate(anns):
-                x, y, w, h = (float(v) for v in ann["bbox"])
-                gt[b, g] = (x, y, w, h, float(ann["area"]) if "area" in ann else w * h)
-                gl[b, g], gi[b, g] = int(ann["category_id"]), int(bool(ann.get("ignore", 0)))
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        self.process_padded(scores, labels, xyxy, torch.tensor(lens, dtype=torch.int32).to(dev), up(gt[:, :, :4]),
-                            up(gt[:, :, 4]), up(gl), up(gi), torch.tensor([len(a) for a in annos], dtype=torch.int32).to(dev),
+        dets = box_eval.pad_instances(outputs)
+        dev, C = dets[0].device, len(self.class_names)
+        self.process_padded(*dets, *box_eval.pad_annotations(inputs, dev, "ignore", with_area=True),
                             category_bitsets([x.get("neg_category_ids", ()) for x in inputs], C, dev),
                             category_bitsets([x.get("not_exhaustive_category_ids", ()) for x in inputs], C, dev))
 
@@ -313,8 +226,6 @@ class LVISBoxEvaluator:
         self._batches.extend(other._batches)
         return self
 
-    _gather = ev.CocoBoxEvaluator._gather       # every kept tensor of the shared state as a host array, one copy per device
-
     def _result(self, precision, recall, n_pred):
         self.precision, self.recall = precision, recall
         if n_pred == 0:                             # the reference: "No predictions from the model! Set scores to -1"
@@ -322,20 +233,12 @@ class LVISBoxEvaluator:
         return {"bbox": summarize(precision, recall, self.frequencies, self.iou_thrs, self.max_dets)}
 
     def evaluate(self):
-        C, max_dets = len(self.class_names), (self.max_dets,)
-        if not FORCE_REFERENCE and ev.accumulate_supported(self._batches, C, self.iou_thrs, self.area_rngs, max_dets):
-            p, r = ev.accumulate_device(self._batches, C, self.iou_thrs, self.area_rngs, max_dets)
+        args = (len(self.class_names), self.iou_thrs, self.area_rngs, (self.max_dets,))
+        if not FORCE_REFERENCE and ev.accumulate_supported(self._batches, *args):
+            p, r = ev.accumulate_device(self._batches, *args)
             n_pred = torch.stack([b["n_pred"] for b in self._batches]).sum().to(torch.float64)      # exact: far below 2^53
-            both = torch.cat([p.view(-1), r.view(-1), n_pred.view(1)]).cpu().numpy()               # ONE device -> host copy
-            precision = both[:p.numel()].reshape(tuple(p.shape))
-            recall = both[p.numel():p.numel() + r.numel()].reshape(tuple(r.shape))
-            return self._result(precision, recall, int(both[-1]))
+            precision, recall, n_pred = box_eval.read_back(p, r, n_pred)                           # ONE device -> host copy
+            return self._result(precision, recall, int(n_pred))
         host = self._gather()
         n_pred = sum(int(b["n_pred"]) for b in self._batches)
-        cat = lambda k, dt: np.concatenate([h[k] for h in host]) if host else np.zeros(0, dt)
-        rank, gt_label = cat("rank", np.int32), cat("gt_label", np.int64)
-        det, gt = rank >= 0, gt_label >= 0
-        precision, recall = ev.accumulate(cat("scores", np.float32)[det].astype(np.float64), cat("labels", np.int64)[det],
-                                          rank[det], cat("matched", np.uint64)[det], cat("ignored", np.uint64)[det], gt_label[gt],
-                                          cat("gt_ignored", np.uint8)[gt], C, self.iou_thrs, self.area_rngs, max_dets)
-        return self._result(precision, recall, n_pred)
+        return self._result(*ev.accumulate(*box_eval.accumulate_inputs(host), *args), n_pred)

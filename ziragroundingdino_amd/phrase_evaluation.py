@@ -13,7 +13,8 @@
 
 ``match`` is one launch for the batch (csrc/phrasematch.hip), without a host read; ``match_reference`` is the same function as
 torch ops on the tensors' own device, for CPU tensors, other dtypes, shapes outside the kernel's limits and the tests.
-``PhraseGroundingEvaluator`` keeps two small integer tensors where the outputs are and reads them once, in ``evaluate()``.
+``PhraseGroundingEvaluator`` keeps two small integer tensors where the outputs are and reads them once, in ``evaluate()``;
+``inference_on_grounding_dataset`` is ``box_eval.run_dataset``, the loop of the box evaluators.
 
 Mask words are int32 tensors that hold the 32 bits of a uint32 word: token ``t`` at bit ``t % 32`` of word ``t // 32``, the layout
 of ``grounding.Grounded.token_bits``."""
@@ -23,7 +24,7 @@ from collections import namedtuple
 
 import torch
 
-from . import _lib
+from . import _lib, box_eval
 from . import grounding
 
 MAX_B, MAX_Q, MAX_T, MAX_P, MAX_G, MAX_K, MAX_THRS = (_lib.PHRASE_CONSTANTS["ZIRA_PHRASE_MAX_" + k]
@@ -343,16 +344,7 @@ class PhraseGroundingEvaluator:
 
 
 def inference_on_grounding_dataset(model, loader, evaluator):
-    """``evaluation.inference_on_dataset`` for the free-text surface: eval mode, no gradients, ``model.forward_grounding`` and
-    ``evaluator.process`` per batch, the model's mode put back.  As ``run_task``'s ``evaluate=``:
+    """``evaluation.inference_on_dataset`` for the free-text surface: ``box_eval.run_dataset`` over
+    ``model.forward_grounding(inputs)``.  As ``run_task``'s ``evaluate=``:
     ``lambda model, spec: inference_on_grounding_dataset(model, loader, evaluator)``."""
-    was_training = model.training
-    model.eval()
-    evaluator.reset()
-    try:
-        with torch.no_grad():
-            for inputs in loader:
-                evaluator.process(inputs, model.forward_grounding(inputs))
-    finally:
-        model.train(was_training)
-    return evaluator.evaluate()
+    return box_eval.run_dataset(model, loader, evaluator, lambda inputs: model.forward_grounding(inputs))

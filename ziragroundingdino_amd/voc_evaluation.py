@@ -10,16 +10,18 @@ and boxes that are matched are the quantised ones ("%.3f", "%.1f" after ``xmin +
 batch, every label and every threshold in one launch (csrc/vocmatch.hip, the rules stated at ``zira_voc_match`` in
 include/zira_msda.h); ``match_reference`` is the same function in numpy fp64 on any device, for what ``match_supported``
 declines, for CPU tensors and for the tests.  ``PascalVOCBoxEvaluator`` keeps the per-batch results on the device and reads
-them back once, in ``evaluate()``, which is the reference's cumulative sums and ``voc_ap`` in numpy fp64.
+them back once, in ``evaluate()``, which is the reference's cumulative sums and ``voc_ap`` in numpy fp64.  The padding of a
+batch and the read-back of the kept state are ``box_eval``'s; the overlap and the walk here are VOC's own and share nothing.
 
 ``tp`` / ``fp`` are int32 tensors that hold the 32 bits of the entry's u32 words (bit ``t``).
 """
 import ctypes
+import sys
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, box_eval
 
 MAX_B, MAX_K, MAX_G, MAX_THRS = 65535, 1024, 1024, _lib.VOC_MAX_THRS
 FORCE_REFERENCE = False     # True: PascalVOCBoxEvaluator matches with match_reference wherever it runs (tests, A/B)
@@ -210,10 +212,11 @@ def accumulate(qscore, labels, tp, fp, gt_label, gt_difficult, num_classes, iou_
 _STATE = ("qscore", "labels", "tp", "fp", "gt_label", "gt_difficult")
 
 
-class PascalVOCBoxEvaluator:
+class PascalVOCBoxEvaluator(box_eval.BoxEvaluator):
     """detectron2's ``DatasetEvaluator`` surface (``reset`` / ``process`` / ``evaluate``) for Pascal VOC box AP, with the
     reference's base / novel split.  ``process`` pads the batch, matches it in one launch and keeps the result where it is;
     nothing is read back before ``evaluate()``."""
+    _STATE, _WORDS, _WORD_DTYPE = _STATE, ("tp", "fp"), np.uint32
 
     def __init__(self, class_names, year=2007, base_classes=None, novel_classes=None, iou_thrs=None):
         if year not in (2007, 2012):
@@ -225,48 +228,20 @@ class PascalVOCBoxEvaluator:
         self.iou_thrs = tuple(float(t) for t in (DEFAULT_IOU_THRS if iou_thrs is None else iou_thrs))
         self.reset()
 
-    def reset(self):
-        self._batches = []
-
     def process_padded(self, scores, labels, xyxy, n_keep, gt_xyxy, gt_label, gt_difficult, n_gt):
         """One batch from raw tensors (``match``'s inputs; rows in any order: the matching orders them itself)."""
-        K, G = scores.shape[1], gt_label.shape[1]
-        dev = scores.device
-        args = (scores, labels, xyxy, n_keep, gt_xyxy, gt_label, gt_difficult, n_gt, len(self.class_names), self.iou_thrs)
-        fn = match if not FORCE_REFERENCE and match_supported(*args) else match_reference
-        qscore, tp, fp, _ = fn(*args, with_gt_of=False)
-        valid = torch.arange(K, device=dev)[None, :] < n_keep[:, None]
-        gt_valid = torch.arange(G, device=dev)[None, :] < n_gt[:, None]
-        self._batches.append(dict(qscore=qscore, labels=torch.where(valid, labels, torch.full_like(labels, -1)), tp=tp, fp=fp,
-                                  gt_label=torch.where(gt_valid, gt_label, torch.full_like(gt_label, -1)),
-                                  gt_difficult=gt_difficult))
+        qscore, tp, fp, _ = box_eval.match_batch(sys.modules[__name__], scores, labels, xyxy, n_keep, gt_xyxy, gt_label, gt_difficult,
+                                                 n_gt, len(self.class_names), self.iou_thrs)
+        self._batches.append(dict(qscore=qscore, labels=box_eval.mask_behind(labels, n_keep), tp=tp, fp=fp,
+                                  gt_label=box_eval.mask_behind(gt_label, n_gt), gt_difficult=gt_difficult))
 
     def process(self, inputs, outputs):
         """``inputs``: the batched_inputs dicts, each with ``"annotations"`` (dicts: ``bbox`` xyxy in VOC's 1-based inclusive
         pixels as the annotation file has them, ``category_id`` the contiguous index, ``difficult``); ``outputs``: what the model
         returns in eval mode, ``[{"instances": Instances}]``."""
-        insts = [o["instances"] for o in outputs]
-        dev = insts[0].scores.device
-        B = len(insts)
-        lens = [len(i) for i in insts]
-        K = max(1, max(lens))
-        scores = torch.zeros((B, K), dtype=torch.float32, device=dev)
-        labels = torch.zeros((B, K), dtype=torch.int64, device=dev)
-        xyxy = torch.zeros((B, K, 4), dtype=torch.float32, device=dev)
-        for b, (inst, n) in enumerate(zip(insts, lens)):
-            scores[b, :n], labels[b, :n], xyxy[b, :n] = inst.scores, inst.pred_classes, inst.pred_boxes.tensor
-        annos = [list(x.get("annotations", ())) for x in inputs]
-        G = max(len(a) for a in annos)
-        gt = np.zeros((B, G, 4))
-        gl = np.zeros((B, G), np.int64)
-        gd = np.zeros((B, G), np.uint8)
-        for b, anns in enumerate(annos):
-            for g, ann in enumerate(anns):
-                gt[b, g] = [float(v) for v in ann["bbox"]]
-                gl[b, g], gd[b, g] = int(ann["category_id"]), int(bool(ann.get("difficult", 0)))
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        self.process_padded(scores, labels, xyxy, torch.tensor(lens, dtype=torch.int32).to(dev), up(gt), up(gl), up(gd),
-                            torch.tensor([len(a) for a in annos], dtype=torch.int32).to(dev))
+        dets = box_eval.pad_instances(outputs)
+        gt_xyxy, _, gt_label, gt_difficult, n_gt = box_eval.pad_annotations(inputs, dets[0].device, "difficult", with_area=False)
+        self.process_padded(*dets, gt_xyxy, gt_label, gt_difficult, n_gt)
 
     def merge(self, other):
         """Append another evaluator's state (a data-parallel run gathers its ranks' evaluators with this, in rank order)."""
@@ -275,27 +250,9 @@ class PascalVOCBoxEvaluator:
         self._batches.extend(other._batches)
         return self
 
-    def _gather(self):
-        """Every kept tensor as a host array, through ONE device -> host copy per device that holds state."""
-        host = [None] * len(self._batches)
-        for dev in {b["qscore"].device for b in self._batches}:
-            idx = [i for i, b in enumerate(self._batches) if b["qscore"].device == dev]
-            flat = [self._batches[i][k].contiguous().view(-1).view(torch.uint8) for i in idx for k in _STATE]
-            blob = torch.cat(flat).cpu().numpy()
-            off = 0
-            for i in idx:
-                host[i] = {}
-                for k in _STATE:
-                    t = self._batches[i][k]
-                    n = t.numel() * t.element_size()
-                    dt = np.uint32 if k in ("tp", "fp") else torch.empty(0, dtype=t.dtype).numpy().dtype
-                    host[i][k] = np.frombuffer(blob[off:off + n].tobytes(), dtype=dt)
-                    off += n
-        return host
-
     def evaluate(self):
         host = self._gather()
-        cat = lambda k, dt: np.concatenate([h[k] for h in host]) if host else np.zeros(0, dt)
+        cat = lambda k, dt: box_eval.concat_state(host, k, dt)
         labels, gt_label = cat("labels", np.int64), cat("gt_label", np.int64)
         det, gt = labels >= 0, gt_label >= 0
         ap = accumulate(cat("qscore", np.float64)[det], labels[det], cat("tp", np.uint32)[det], cat("fp", np.uint32)[det],
