@@ -9,7 +9,8 @@ pytestmark = pytest.mark.gpu
 from ziragroundingdino_amd import backbone as zb  # noqa: E402
 
 
-@pytest.mark.parametrize("H,W,ws,heads", [(14, 21, 7, 3), (20, 17, 7, 6), (7, 7, 7, 2), (25, 30, 12, 4), (50, 84, 7, 12)])
+@pytest.mark.parametrize("H,W,ws,heads", [(14, 21, 7, 3), (20, 17, 7, 6), (7, 7, 7, 2), (25, 30, 12, 4), (50, 84, 7, 12),
+                                          (9, 10, 4, 2), (17, 9, 8, 1)])   # (the last two: the one-wave-per-window vector kernel)
 def test_swin_layer_native_attention_equals_pytorch_path(H, W, ws, heads):
     torch.manual_seed(H * 100 + W)
     dim = heads * 32

@@ -181,8 +181,9 @@ class WindowAttention(nn.Module):
 class SwinTransformerBlock(nn.Module):
     native_max_tokens = 64
     native_attention = True   # no-grad GPU forwards: window attention through the C ABI (csrc/winattn.hip) -- fp32 with
-                              # windows of <= 64 tokens (7x7: one query row per lane) and, fp32 or under bf16 autocast,
-                              # the 12x12 windows of the 384-pixel Swin-B / L variants (144 tokens: the MFMA kernel)
+                              # windows of <= 64 tokens (7x7: the MFMA kernel; other sizes: one query row per lane) and,
+                              # fp32 or under bf16 autocast, the 12x12 windows of the 384-pixel Swin-B / L variants (144
+                              # tokens: the MFMA kernel)
 
     def _native_ok(self, x, C):
         ws = self.window_size

@@ -1,7 +1,8 @@
 // adapter.hip -- the gated bottleneck adapter beside the FFN of the deformable encoder / decoder layers, forward and backward
 // (C ABI and the defining formulas: include/zira_adapter.h; reference models/GroundingDINO/adapter.py:124-179).
 //
-// One wave owns 32 rows, a block of four waves a panel of 128.  Every product is v_mfma_f32_32x32x2_f32 with fp32 accumulation.
+// One wave owns 32 rows, a block of four waves a panel of 128.  Every product is v_mfma_f32_32x32x2_f32 with fp32 accumulation,
+// in the orientation of csrc/mfma_f32_tile.h.
 // The instruction's reduction index is free as long as both operands agree on it, so lane (r, hh) holds the CONTIGUOUS 32 floats
 // [64 c + 32 hh, +32) of row r of a 64-wide slice c of the left operand -- eight 16-byte loads straight from global memory, each
 // row read once -- and the weight operand is read with the same index map (L2-resident: 64 KB per matrix).
@@ -18,12 +19,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mfma_f32_tile.h"
 #include "zira_adapter.h"
 #include "zira_msda.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kD = 256, kH = 64, kMaxG = 8;
 constexpr int kWaveRows = 32, kWaves = 4, kPanel = kWaveRows * kWaves, kThreads = 64 * kWaves;
@@ -32,25 +32,6 @@ constexpr int kPS = kWaveRows + 1;                   // LDS stride of the row-do
 constexpr int kWavePart = kD + kMaxG * kD;           // g_b_up, g_gate: floats a wave carries out of the row-major pass
 constexpr int kBwdPart = kH + kWavePart;             // doubles a block leaves: g_b_down, g_b_up, g_gate
 constexpr long long kMaxM = 1ll << 22;
-
-__device__ __forceinline__ int rowmap(int reg, int hh) { return (reg & 3) + 8 * (reg >> 2) + 4 * hh; }
-
-__device__ __forceinline__ void load32(float (&dst)[32], const float *src)
-{
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float4 v = *reinterpret_cast<const float4 *>(src + 4 * i);
-        dst[4 * i] = v.x; dst[4 * i + 1] = v.y; dst[4 * i + 2] = v.z; dst[4 * i + 3] = v.w;
-    }
-}
-
-__device__ __forceinline__ f32x16 zero16()
-{
-    f32x16 z;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) z[e] = 0.f;
-    return z;
-}
 
 // gs[g][:] = gate[g] / |gate[g]| for g < G, zeros above; ginv[g] = 1 / |gate[g]|.  Wave w takes rows w and w + 4.
 __device__ __forceinline__ void normalise_gate(const float *__restrict__ gate, int G, float *gs, float *ginv, int wave, int lane)
@@ -104,7 +85,7 @@ __global__ __launch_bounds__(kThreads) void adapter_fwd(const float *__restrict_
     for (int c = 0; c < kD / 64; ++c) {
         const int k0 = 64 * c + 32 * hh;
         float xa[32];
-        load32(xa, x + (size_t)rowc * kD + k0);
+        load_floats(x + (size_t)rowc * kD + k0, xa);
         // the slice's sums on their own, then into the totals: no chain of additions is longer than 32 + 4
         float ss_l = 0.f, ab_l = 0.f;
 #pragma unroll
@@ -125,16 +106,15 @@ __global__ __launch_bounds__(kThreads) void adapter_fwd(const float *__restrict_
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             float wb[32];
-            load32(wb, Wd + (size_t)(32 * j + r) * kD + k0);
-#pragma unroll
-            for (int t = 0; t < 32; ++t) acc[j][c & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[t], wb[t], acc[j][c & 1], 0, 0, 0);
+            load_floats(Wd + (size_t)(32 * j + r) * kD + k0, wb);
+            mfma_chain<32>(xa, wb, acc[j][c & 1]);
         }
     }
     // the two halves of a row meet: both lanes of the row hold the same totals afterwards
     const float ab_half = ab;
-    ss += __shfl_xor(ss, 32, 64);
+    ss += xhalf(ss);
 #pragma unroll
-    for (int g = 0; g < kMaxG; ++g) dg[g] += __shfl_xor(dg[g], 32, 64);
+    for (int g = 0; g < kMaxG; ++g) dg[g] += xhalf(dg[g]);
     const float norm = sqrtf(ss);
     float cmax = 0.f, scale = base;
     int amax = 0;
@@ -185,9 +165,8 @@ __global__ __launch_bounds__(kThreads) void adapter_fwd(const float *__restrict_
         for (int jj = 0; jj < 2; ++jj) {
             o[jj] = zero16();
             float wb[32];
-            load32(wb, Wu + (size_t)(64 * jp + 32 * jj + r) * kH + 32 * hh);
-#pragma unroll
-            for (int t = 0; t < 32; ++t) o[jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(ha[t], wb[t], o[jj], 0, 0, 0);
+            load_floats(Wu + (size_t)(64 * jp + 32 * jj + r) * kH + 32 * hh, wb);
+            mfma_chain<32>(ha, wb, o[jj]);
         }
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
@@ -275,8 +254,8 @@ __global__ __launch_bounds__(kThreads) void adapter_bwd_rows(const float *__rest
     for (int c = 0; c < kD / 64; ++c) {
         const int k0 = 64 * c + 32 * hh;
         float ga[32], bb[32];
-        load32(ga, gy + (size_t)rowc * kD + k0);
-        load32(bb, bu + k0);
+        load_floats(gy + (size_t)rowc * kD + k0, ga);
+        load_floats(bu + k0, bb);
         float gb_l = 0.f;
 #pragma unroll
         for (int t = 0; t < 32; ++t) gb_l = fmaf(ga[t], bb[t], gb_l);
@@ -287,7 +266,7 @@ __global__ __launch_bounds__(kThreads) void adapter_bwd_rows(const float *__rest
             for (int t = 0; t < 32; ++t)
                 acc[j][c & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[t], Wu[(size_t)(k0 + t) * kH + 32 * j + r], acc[j][c & 1], 0, 0, 0);
     }
-    gb += __shfl_xor(gb, 32, 64);
+    gb += xhalf(gb);
 
     // ---- gh, scale * h, the row dots' pieces, g_b_down ------------------------------------------------------------------------------
     float p[16], gbd[2];
@@ -317,7 +296,7 @@ __global__ __launch_bounds__(kThreads) void adapter_bwd_rows(const float *__rest
     for (int reg = 0; reg < 16; ++reg) dots[rowmap(reg, hh) * kPS + r] = p[reg];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        gbd[j] += __shfl_xor(gbd[j], 32, 64);
+        gbd[j] += xhalf(gbd[j]);
         if (hh == 0) bdp[wave][32 * j + r] = gbd[j];
     }
     __syncthreads();

@@ -6,14 +6,8 @@
 // backward per layer on MI355X (six score-sized tensors of 52 MB each go through HBM, the batched 900 x 32 x 900
 // products run at 26 TF/s); the arithmetic is 1.7 + 4.1 GFLOP.  Here the scores never leave registers.
 //
-// Everything is built on `v_mfma_f32_32x32x2_f32` (exact fp32 products, fp32 accumulation: the numerics of an fmaf
-// chain) with the operand ORIENTATION chosen so that no tile is ever transposed or moved between lanes:
-//   * a 32 x 32 result has its column on the lane (lane & 31) and 16 of its rows in the lane's registers
-//     (row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)); at contraction step t the two lane halves supply the two
-//     k-indices, and WHICH two is free as long as both operands agree -- so half h uses feature 16 h + t when the
-//     contraction runs over the 32 features (a lane loads a contiguous half row), and row (t & 3) + 8 (t >> 2) + 4 h
-//     of a previous result when it runs over that result's rows: register t of the previous accumulator IS the
-//     operand, untouched.
+// Everything is built on `v_mfma_f32_32x32x2_f32` in the orientation of csrc/mfma_f32_tile.h (a result's column on the lane, 16
+// of its rows in the lane's registers, no tile ever transposed or moved between lanes):
 //   * forward and dQ: S^T = K Q^T (keys x queries): a query's scores sit in ONE lane (two, with the other half), so
 //     the softmax statistics are per-lane scalars; O^T += V^T P^T and dQ^T += K^T dS^T sum over S^T's rows.
 //   * dK / dV: S = Q K^T (queries x keys): dV^T += dO^T P and dK^T += Q^T dS sum over S's rows.
@@ -36,16 +30,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mfma_f32_tile.h"
 #include "zira_msda.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kD = 32;
-
-__device__ __forceinline__ unsigned rowmap(unsigned reg, unsigned hh) { return (reg & 3u) + 8u * (reg >> 2) + 4u * hh; }
-__device__ __forceinline__ float xhalf(float x) { return __shfl_xor(x, 32); }
 
 struct AttnDims {
     int L, S, B, H;
@@ -58,12 +48,7 @@ struct AttnDims {
 __device__ __forceinline__ void load_half_row(const float *__restrict__ p, int row, int b, int B, int ld, int h, unsigned hh,
                                               float (&x)[16])
 {
-    const float4 *src = reinterpret_cast<const float4 *>(p + ((size_t)row * B + b) * ld + h * kD + 16 * hh);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float4 v = src[i];
-        x[4 * i] = v.x; x[4 * i + 1] = v.y; x[4 * i + 2] = v.z; x[4 * i + 3] = v.w;
-    }
+    load_floats(p + ((size_t)row * B + b) * ld + h * kD + 16 * hh, x);
 }
 // x[t] = element `col` of row base + rowmap(t, hh) (clamped to nrows - 1)
 __device__ __forceinline__ void load_column(const float *__restrict__ p, int base, int nrows, int b, int B, int ld, int h,
@@ -102,9 +87,7 @@ __global__ __launch_bounds__(256) void attn_fwd(const float *__restrict__ q, con
         for (int t = 0; t < 16; ++t) bq[t] *= A.scale;
     }
     float m = -INFINITY, lsum = 0.f;
-    f32x16 acc_o;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc_o[i] = 0.f;
+    f32x16 acc_o = zero16();
 
     for (int kt = KSPLIT == 4 ? (int)wave : 0; kt < nkt; kt += KSPLIT == 4 ? 4 : 1) {
         const int k0 = kt * 32;
@@ -114,9 +97,7 @@ __global__ __launch_bounds__(256) void attn_fwd(const float *__restrict__ q, con
             load_half_row(k, kr, b, A.B, A.ldk, h, hh, ka);
         }
         load_column(v, k0, A.S, b, A.B, A.ldv, h, hh, r, va);
-        f32x16 s;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = 0.f;
+        f32x16 s = zero16();
 #pragma unroll
         for (int t = 0; t < 16; ++t) s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[t], bq[t], s, 0, 0, 0);
         // s[reg] = S^T[key k0 + rowmap(reg, hh)][query q0 + r]
@@ -234,9 +215,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(const float *__restrict__ q, 
     for (int t = 0; t < 16; ++t) bq[t] *= A.scale;
     const float lq = lse[(size_t)bh * A.L + qr];
     if (wave == 0 && hh == 0 && q0 + (int)r < A.L) delta[(size_t)bh * A.L + q0 + r] = dl;
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    f32x16 acc = zero16();
 
     for (int kt = (int)wave; kt < nkt; kt += 4) {
         const int k0 = kt * 32;
@@ -245,9 +224,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(const float *__restrict__ q, 
         load_half_row(k, kr, b, A.B, A.ldk, h, hh, ka);
         load_half_row(v, kr, b, A.B, A.ldv, h, hh, vr);
         load_column(k, k0, A.S, b, A.B, A.ldk, h, hh, r, kc);
-        f32x16 s, dp;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
+        f32x16 s = zero16(), dp = zero16();
 #pragma unroll
         for (int t = 0; t < 16; ++t) s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[t], bq[t], s, 0, 0, 0);
 #pragma unroll

@@ -6,7 +6,7 @@
 // blocks of 32, the last one partly filled), so every product of the wave is with that image's text.  Every product is
 // v_mfma_f32_32x32x2_f32 with fp32 accumulation, and every matrix is kept TRANSPOSED in the accumulators -- the row on the lane,
 // the feature (or token) index in the registers: an accumulator tile is then the B operand of the next product as it stands
-// (the instruction's reduction index is free as long as both operands agree on it), with no trip through LDS.
+// (the instruction's reduction index is free as long as both operands agree on it: csrc/mfma_f32_tile.h), with no trip through LDS.
 //
 // forward   zT = W xT + bias (eight 32 x 32 tiles: the 256 features of the wave's rows, 128 registers);  per panel of 32 tokens
 //           lT = text zT, the text rows read straight from global memory (L2-resident: 256 KB per image at most) in the feature
@@ -23,34 +23,14 @@
 #include <stdint.h>
 
 #include "cat_max.h"
+#include "mfma_f32_tile.h"
 #include "zira_clslinear.h"
 #include "zira_msda.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kD = 256, kTiles = kD / 32, kRows = 32, kThreads = 64, kMaxT = 256, kMaxC = 256;
 constexpr long long kMaxR = 1ll << 22;
-
-__device__ __forceinline__ int rowmap(int reg, int hh) { return (reg & 3) + 8 * (reg >> 2) + 4 * hh; }
-
-__device__ __forceinline__ void load32(float (&dst)[32], const float *src)
-{
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float4 v = *reinterpret_cast<const float4 *>(src + 4 * i);
-        dst[4 * i] = v.x; dst[4 * i + 1] = v.y; dst[4 * i + 2] = v.z; dst[4 * i + 3] = v.w;
-    }
-}
-
-__device__ __forceinline__ f32x16 zero16()
-{
-    f32x16 z;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) z[e] = 0.f;
-    return z;
-}
 
 // the wave's place: block -> (prediction set and image, block of 32 queries)
 struct Place {
@@ -98,13 +78,12 @@ __global__ __launch_bounds__(kThreads) void cls_linear_fwd(const float *__restri
         for (int c = 0; c < kD / 64; ++c) {
             const int k0 = 64 * c + 32 * hh;
             float xa[32];
-            load32(xa, x + (size_t)rowc * kD + k0);
+            load_floats(x + (size_t)rowc * kD + k0, xa);
 #pragma unroll
             for (int j = 0; j < kTiles; ++j) {
                 float wb[32];
-                load32(wb, W + (size_t)(32 * j + r) * kD + k0);
-#pragma unroll
-                for (int t = 0; t < 32; ++t) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[t], xa[t], acc[j], 0, 0, 0);
+                load_floats(W + (size_t)(32 * j + r) * kD + k0, wb);
+                mfma_chain<32>(wb, xa, acc[j]);
             }
         }
 #pragma unroll

@@ -16,11 +16,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mfma_f32_tile.h"
 #include "zira_msda.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #ifndef ZIRA_GD_BK
 #define ZIRA_GD_BK 16
@@ -34,8 +33,6 @@ constexpr int kBM = 128, kBN = 128, kBK = ZIRA_GD_BK, kThreads = 256;
 // wave writes at a time (16 columns each) into four different quarters -- no bank conflicts either way (a padded stride
 // of 132 had every operand read two-way conflicted, with the LDS the busiest unit of the CU).
 __device__ __forceinline__ int swz(int k, int x) { return k * 128 + ((x + 16 * (k >> 2) + 32 * (k & 1)) & 127); }
-
-__device__ __forceinline__ unsigned rowmap(unsigned reg, unsigned hh) { return (reg & 3u) + 8u * (reg >> 2) + 4u * hh; }
 
 // A [M, K] row-major (lda), B [K, N] row-major (ldb), H / C [M, N] row-major (ldc).  N % 128 == 0, K % 16 == 0.
 __global__ __launch_bounds__(kThreads, ZIRA_GD_OCC) void gemm_nn_drelu(const float *__restrict__ A, const float *__restrict__ B,
@@ -64,9 +61,7 @@ __global__ __launch_bounds__(kThreads, ZIRA_GD_OCC) void gemm_nn_drelu(const flo
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        for (int j = 0; j < 2; ++j) acc[i][j] = zero16();
 
     auto stage = [&](int buf) {
         As[buf][swz(ak + 0, am)] = ga0.x; As[buf][swz(ak + 1, am)] = ga0.y; As[buf][swz(ak + 2, am)] = ga0.z; As[buf][swz(ak + 3, am)] = ga0.w;
@@ -117,7 +112,7 @@ __global__ __launch_bounds__(kThreads, ZIRA_GD_OCC) void gemm_nn_drelu(const flo
         }
     }
 
-    // epilogue: acc[i][j][reg] = (A B)[bm + wr * 64 + 32 i + rowmap(reg, hh)][bn + wc * 64 + 32 j + r].  The accumulator
+    // epilogue: acc[i][j][reg] = (A B)[bm + wr * 64 + 32 i + rowmap(reg, hh)][bn + wc * 64 + 32 j + r] (mfma_f32_tile.h).  The accumulator
     // layout has a lane per column; a 16 x 64 slab at a time goes through the wave's quarter of the (now idle) operand
     // buffers and comes back a row segment per 16 lanes, so that h is read and C written with 16-byte accesses (a dword
     // per lane and element took 128 memory instructions per lane and 63 us of the kernel; this form 32: 500 -> 480 us).

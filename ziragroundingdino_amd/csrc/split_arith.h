@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "mfma_f32_tile.h"   // f32x16
+
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -18,7 +20,6 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---- f16, two planes ----------------------------------------------------------------------------------------------------------------
 

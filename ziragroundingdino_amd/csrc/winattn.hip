@@ -11,13 +11,15 @@
 // q/k/v are the projection's bias, since the reference pads the normalised map with zeros), the bias comes from a
 // small [heads, N, N] table, the shift mask from the token's region id.
 //
-// One wavefront per (image, window, head): k and v of the window's N tokens are staged in LDS, lane r < N owns query
-// row r and runs an online softmax over the N keys (every lane reads the same k_j / v_j: LDS broadcast), 32-wide
-// accumulator in registers (head_dim = 32 in every Swin variant).  fp32 throughout.
+// 7 x 7 and 12 x 12 windows run on the matrix cores (window_attn_mfma, below).  Every other window up to 14 x 14 takes
+// window_attn_kernel: one wavefront per (image, window, head), k and v of the window's N tokens staged in LDS, lane r < N owns
+// query row r and runs an online softmax over the N keys, a key per step (every lane reads the same k_j / v_j: LDS broadcast),
+// 32-wide accumulator in registers (head_dim = 32 in every Swin variant).  fp32 throughout.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mfma_f32_tile.h"
 #include "zira_msda.h"
 
 namespace {
@@ -31,7 +33,6 @@ __device__ __forceinline__ int region(int x, int Xp, int ws, int shift)
     return x < Xp - ws ? 0 : (x < Xp - shift ? 1 : 2);
 }
 
-template <int kChunk>   // 7: 7 x 7 windows, a window row of keys per softmax step; 0: any window up to 16 x 16, a key per step
 __global__ __launch_bounds__(256) void window_attn_kernel(const float *__restrict__ qkv, const float *__restrict__ qkv_bias,
                                                           const float *__restrict__ bias_t, int B, int H, int W, int heads,
                                                           int ws, int shift, float scale, int nitems, int lds_per_wave,
@@ -86,48 +87,6 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const float *__restric
             o[c] = o[c + 1] = o[c + 2] = o[c + 3] = 0.f;
         }
         float m = -INFINITY, l = 0.f;
-        if (kChunk > 0) {
-            // Online softmax a window row (kChunk keys) at a time: the accumulator is rescaled once per chunk instead of once
-            // per key (o * corr + p * v is two instructions per output pair), and a dot product runs on two packed
-            // accumulators instead of one 32-long dependent chain.
-            for (int j0 = 0; j0 < N; j0 += kChunk) {
-                float sc[kChunk > 0 ? kChunk : 1];
-                float mc = m;
-#pragma unroll
-                for (int jj = 0; jj < kChunk; ++jj) {
-                    const int j = j0 + jj;
-                    const float *kj = ks + j * kRowPad;
-                    float2 a0 = make_float2(0.f, 0.f), a1 = make_float2(0.f, 0.f);
-#pragma unroll
-                    for (int c = 0; c < kHD; c += 4) {
-                        const float4 k4 = *reinterpret_cast<const float4 *>(kj + c);
-                        a0.x = fmaf(q[c], k4.x, a0.x); a0.y = fmaf(q[c + 1], k4.y, a0.y);
-                        a1.x = fmaf(q[c + 2], k4.z, a1.x); a1.y = fmaf(q[c + 3], k4.w, a1.y);
-                    }
-                    float sj = (a0.x + a0.y) + (a1.x + a1.y) + bt[(size_t)j * N + r];
-                    if (shift && reg[j] != rid) sj -= 100.0f;
-                    sc[jj] = sj;
-                    mc = fmaxf(mc, sj);
-                }
-                const float corr = __expf(m - mc);
-                l *= corr;
-#pragma unroll
-                for (int c = 0; c < kHD; ++c) o[c] *= corr;
-#pragma unroll
-                for (int jj = 0; jj < kChunk; ++jj) {
-                    const float p = __expf(sc[jj] - mc);
-                    l += p;
-                    const float *vj = vs + (j0 + jj) * kRowPad;
-#pragma unroll
-                    for (int c = 0; c < kHD; c += 4) {
-                        const float4 v4 = *reinterpret_cast<const float4 *>(vj + c);
-                        o[c] = fmaf(p, v4.x, o[c]); o[c + 1] = fmaf(p, v4.y, o[c + 1]);
-                        o[c + 2] = fmaf(p, v4.z, o[c + 2]); o[c + 3] = fmaf(p, v4.w, o[c + 3]);
-                    }
-                }
-                m = mc;
-            }
-        } else
         for (int j = 0; j < N; ++j) {
             const float *kj = ks + j * kRowPad;
             float s = 0.f;
@@ -160,20 +119,15 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const float *__restric
     }
 }
 
-
 // ------------------------------------------------------------------------------------------
 // 12 x 12 windows (the 384-pixel Swin-B / L variants: 144 tokens per window) on the matrix cores
 // ------------------------------------------------------------------------------------------
 // One block per (image, window, head), one wave per tile of 32 queries (five for 144 tokens).  The block stages the
 // window's K and V rows (padding tokens: the projection's bias) and the tokens' shift-mask regions in LDS once; every
-// wave then walks the five key tiles in the MFMA form of csrc/attn.hip: S^T = K Q^T on `v_mfma_f32_32x32x2_f32` (exact
-// fp32 products) with a query's scores in ONE lane's accumulator registers -- bias, mask, running maximum and sum are
-// per-lane scalars -- and O^T += V^T P^T takes those registers directly as its operand.  Input / output either fp32 or
+// wave then walks the five key tiles in the orientation of csrc/mfma_f32_tile.h, as csrc/attn.hip's forward does: S^T = K Q^T
+// with a query's scores in ONE lane's accumulator registers -- bias, mask, running maximum and sum are per-lane scalars -- and
+// O^T += V^T P^T takes those registers directly as its operand.  Input / output either fp32 or
 // bf16 (configs[3] runs the qkv projection under bf16 autocast; the arithmetic here is fp32 either way).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ unsigned rowmap32(unsigned reg, unsigned hh) { return (reg & 3u) + 8u * (reg >> 2) + 4u * hh; }
-
 __device__ __forceinline__ float bf16_to_f32(unsigned short x) { return __uint_as_float((unsigned)x << 16); }
 __device__ __forceinline__ unsigned short f32_to_bf16(float x)   // round to nearest even (torch's conversion)
 {
@@ -182,16 +136,8 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float x)   // round to nea
     u += 0x7FFFu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
 }
-// 16 consecutive elements as floats
-__device__ __forceinline__ void load16(const float *p, float (&x)[16])
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float4 v = reinterpret_cast<const float4 *>(p)[i];
-        x[4 * i] = v.x; x[4 * i + 1] = v.y; x[4 * i + 2] = v.z; x[4 * i + 3] = v.w;
-    }
-}
-__device__ __forceinline__ void load16(const unsigned short *p, float (&x)[16])
+// 16 consecutive bfloat16 elements as floats (load_floats for a bf16 tensor)
+__device__ __forceinline__ void load_floats(const unsigned short *p, float (&x)[16])
 {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -208,7 +154,7 @@ __device__ __forceinline__ void load16(const unsigned short *p, float (&x)[16])
 template <typename T>
 __device__ __forceinline__ void load16_bias(const float *p, float (&x)[16])
 {
-    load16(p, x);
+    load_floats(p, x);
     if (sizeof(T) == 2) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) x[i] = bf16_to_f32(f32_to_bf16(x[i]));
@@ -246,7 +192,7 @@ __global__ __launch_bounds__(64 * ((WS * WS + 31) / 32)) void window_attn_mfma(
         const int tok = toks[t];
         float x[16];
         const size_t off = (size_t)(1 + which) * C + h * kHD + 16 * half;
-        if (tok >= 0) load16(qkv + (size_t)tok * 3 * C + off, x);
+        if (tok >= 0) load_floats(qkv + (size_t)tok * 3 * C + off, x);
         else load16_bias<T>(qkv_bias + off, x);
         float *dst = (which ? vs[t] : ks[t]) + 16 * half;
 #pragma unroll
@@ -258,7 +204,7 @@ __global__ __launch_bounds__(64 * ((WS * WS + 31) / 32)) void window_attn_mfma(
     float bq[16];
     {
         const size_t off = (size_t)h * kHD + 16 * hh;
-        if (tokq >= 0) load16(qkv + (size_t)tokq * 3 * C + off, bq);
+        if (tokq >= 0) load_floats(qkv + (size_t)tokq * 3 * C + off, bq);
         else load16_bias<T>(qkv_bias + off, bq);
 #pragma unroll
         for (int t = 0; t < 16; ++t) bq[t] *= scale;
@@ -267,9 +213,7 @@ __global__ __launch_bounds__(64 * ((WS * WS + 31) / 32)) void window_attn_mfma(
 
     const float *bt = bias_t + (size_t)h * N * N;   // [key j][query i]
     float m = -INFINITY, lsum = 0.f;
-    f32x16 acc_o;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc_o[i] = 0.f;
+    f32x16 acc_o = zero16();
     for (int kt = 0; kt < NT; ++kt) {
         const int k0 = kt * 32;
         float ka[16], va[16];
@@ -282,20 +226,18 @@ __global__ __launch_bounds__(64 * ((WS * WS + 31) / 32)) void window_attn_mfma(
             }
 #pragma unroll
             for (unsigned t = 0; t < 16; ++t) {
-                const int vr = k0 + (int)rowmap32(t, hh);
+                const int vr = k0 + (int)rowmap(t, hh);
                 va[t] = vs[vr < N ? vr : N - 1][r];
             }
         }
-        f32x16 s;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = 0.f;
+        f32x16 s = zero16();
 #pragma unroll
         for (int t = 0; t < 16; ++t) s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[t], bq[t], s, 0, 0, 0);
         // s[reg] = S^T[key k0 + rowmap(reg, hh)][query tq]
         float mt = -INFINITY;
 #pragma unroll
         for (unsigned reg = 0; reg < 16; ++reg) {
-            const int kidx = k0 + (int)rowmap32(reg, hh);
+            const int kidx = k0 + (int)rowmap(reg, hh);
             float x = s[reg];
             if (kidx >= N) {
                 x = -INFINITY;
@@ -306,7 +248,7 @@ __global__ __launch_bounds__(64 * ((WS * WS + 31) / 32)) void window_attn_mfma(
             s[reg] = x;
             mt = fmaxf(mt, x);
         }
-        mt = fmaxf(mt, __shfl_xor(mt, 32));
+        mt = fmaxf(mt, xhalf(mt));
         const float m_new = fmaxf(m, mt);
         const float alpha = __expf(m - m_new);   // (m = -inf: 0; every tile holds real keys, so m_new is finite)
         float ps = 0.f;
@@ -324,7 +266,7 @@ __global__ __launch_bounds__(64 * ((WS * WS + 31) / 32)) void window_attn_mfma(
         // acc_o[reg] = O^T[feature rowmap(reg, hh)][query tq]
         m = m_new;
     }
-    lsum += __shfl_xor(lsum, 32);
+    lsum += xhalf(lsum);
     if (tq < N && tokq >= 0) {     // (the reference crops the padding away again)
         const float inv = 1.0f / lsum;
         T *o = out + (size_t)tokq * C + h * kHD;
@@ -372,10 +314,7 @@ int zira_window_attn_f32(const float *qkv, const float *qkv_bias, const float *b
         shift >= window)
         return ZIRA_MSDA_EINVAL;
     if (!qkv || !qkv_bias || !bias_t || !out) return ZIRA_MSDA_EINVAL;
-#ifndef ZIRA_WINATTN_MFMA7
-#define ZIRA_WINATTN_MFMA7 1   // 7 x 7 windows on the matrix-core kernel as well (0: the one-wave-per-window vector kernel)
-#endif
-    if (window == 12 || (window == 7 && ZIRA_WINATTN_MFMA7))   // the MFMA kernel
+    if (window == 7 || window == 12)   // the MFMA kernel
         return launch_window_attn<float>(qkv, qkv_bias, bias_t, B, H, W, heads, window, shift, scale, out, (hipStream_t)stream);
     const int N = window * window;
     const int nwx = (W + window - 1) / window, nwy = (H + window - 1) / window;
@@ -386,14 +325,8 @@ int zira_window_attn_f32(const float *qkv, const float *qkv_bias, const float *b
     if (waves > 4) waves = 4;
     if (waves < 1) return ZIRA_MSDA_EINVAL;
     const unsigned blocks = (unsigned)((nitems + waves - 1) / waves);
-    if (window == 7)
-        hipLaunchKernelGGL(window_attn_kernel<7>, dim3(blocks), dim3(waves * 64), (size_t)waves * lds_per_wave * 4,
-                           (hipStream_t)stream, qkv, qkv_bias, bias_t, B, H, W, heads, window, shift, scale, (int)nitems,
-                           lds_per_wave, out);
-    else
-        hipLaunchKernelGGL(window_attn_kernel<0>, dim3(blocks), dim3(waves * 64), (size_t)waves * lds_per_wave * 4,
-                           (hipStream_t)stream, qkv, qkv_bias, bias_t, B, H, W, heads, window, shift, scale, (int)nitems,
-                           lds_per_wave, out);
+    hipLaunchKernelGGL(window_attn_kernel, dim3(blocks), dim3(waves * 64), (size_t)waves * lds_per_wave * 4, (hipStream_t)stream, qkv,
+                       qkv_bias, bias_t, B, H, W, heads, window, shift, scale, (int)nitems, lds_per_wave, out);
     return (int)hipGetLastError();
 }
 

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "launch.h"
+#include "mfma_f32_tile.h"
 #include "zira_msda.h"
 
 namespace {
@@ -23,7 +24,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxChunks = 128;
 
-typedef float v16f __attribute__((ext_vector_type(16)));
 // 16-byte load from a 4-byte aligned address (rows of odd length): one global_load_dwordx4 on gfx950
 __device__ __forceinline__ float4 load4_unaligned(const float *p)
 {
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void xty_partial(const float *__restrict_
     const bool ia[2] = {a0 + c < a, a0 + 32 + c < a};
     const bool jb[2] = {b0 + c < b, b0 + 32 + c < b};
 
-    v16f acc[2][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(kThreads) void xty_rows128(const float *__restrict_
     const int n_end = (n_begin + chunk_rows < N) ? n_begin + chunk_rows : N;
     const int nsteps = n_end > n_begin ? (n_end - n_begin + 7) / 8 : 0;   // a step = 8 rows: a pair per wave
 
-    v16f acc[IA][JB];
+    f32x16 acc[IA][JB];
 #pragma unroll
     for (int i = 0; i < IA; ++i)
 #pragma unroll
