@@ -90,7 +90,8 @@ class GroundingDINO(nn.Module):
                  use_cls_linear=False, use_prompt_tuning=False, use_prompt_memory_output=True,
                  use_project_tuning=False, use_project_adapter=True,
                  use_zero_inter_loss_for_conv=True, use_learned_names=False,
-                 bert=None, tokenizer=None, side_branch="rep", use_adapter=False, use_self_kd=False, **_unused):
+                 bert=None, tokenizer=None, side_branch="rep", use_adapter=False, use_self_kd=False,
+                 text_branch="rep", cet_type="Adapter", cet_middle_dim=1024, zero_loss_type="L1", **_unused):
         super().__init__()
         assert query_dim == 4 and iter_update, "GroundingDINO uses 4-d queries with iterative update"
         assert two_stage_type in ["no", "standard"]
@@ -128,6 +129,21 @@ class GroundingDINO(nn.Module):
         # ablation (groundingdino_dual_zero_rep_multilayer_branch.py, rsb_multilayer.py)
         assert side_branch in ("rep", "multilayer")
         self.side_branch = side_branch
+        # "rep": ZiRa's RepZeroLinear beside feat_map; "cet": the sibling class's trained text adapter in its place
+        # (groundingdino_dt.py:182-215, cet.py) -- ``use_cet`` then builds ``cet_adapter``, which nothing merges
+        assert text_branch in ("rep", "cet")
+        if text_branch == "cet":
+            from . import cet
+
+            if side_branch != "rep":
+                raise ValueError('text_branch="cet" goes with side_branch="rep": the multilayer ablation has a language branch of its own')
+            if zero_loss_type not in cet.LOSS_CODES:
+                raise NotImplementedError("zero_loss_type %r: one of L1, L2, Smooth_L1" % (zero_loss_type,))
+            if use_prompt_memory and zero_loss_type != "L1":
+                raise NotImplementedError("use_prompt_memory with zero_loss_type %r: the memory loss (prompt.memory_loss) is the L1 "
+                                          "mean only" % (zero_loss_type,))
+            self.cet_type, self.zero_loss_type = cet_type, zero_loss_type
+        self.text_branch = text_branch
         if side_branch == "multilayer":  # unconditional language branch, its own name (reference :322-323)
             from . import rsb_multilayer
 
@@ -135,7 +151,9 @@ class GroundingDINO(nn.Module):
             conv_branch = rsb_multilayer.RepZeroConv2dGN
         else:
             conv_branch = RepZeroConv2d
-            if use_cet:  # RSB #1: language side branch beside feat_map
+            if use_cet and text_branch == "cet":
+                self.cet_adapter = cet.build_cet_adapter(cet_type, self.bert.config.hidden_size, cet_middle_dim, hidden_dim)
+            elif use_cet:  # RSB #1: language side branch beside feat_map
                 self.rep_linear_adapter = RepZeroLinear(self.bert.config.hidden_size, hidden_dim)
         self.specical_tokens = self.tokenizer.convert_tokens_to_ids(["[CLS]", "[SEP]", ".", "?"])
 
@@ -413,11 +431,24 @@ class GroundingDINO(nn.Module):
           entry (:521-531).  Two departures from groundingdino_dt.py: ``use_prompt_memory_output`` alone does nothing (its
           default here is True, and making it live by itself would change every existing evaluation), and the side branch keeps
           running in eval (the dual-branch class this package mirrors always runs it; after the merge it is the 1e-8
-          initialisation)."""
+          initialisation).
+
+        With ``text_branch="cet"`` (:499-507): ``feat_map`` first, then the CET adapter on the BERT STATES (not on the projected
+        text), added to the projected text, with its zero-interference term as the second return value (cet.cet_apply).  It
+        runs only when ``self.training or not self.use_prompt_memory_output``: as in the reference, an eval-mode forward under
+        the default ``use_prompt_memory_output=True`` skips the adapter altogether -- the stored rows are meant to stand in for
+        it -- and the encoded text is ``feat_map``'s alone (the eval substitution itself keeps this package's condition: both
+        ``use_prompt_memory`` and ``use_prompt_memory_output``)."""
         L = self.max_text_len
         encoded_text = self.feat_map(bert_hidden)
         loss_linear_adapter = None
-        if self.side_branch == "multilayer":
+        if self.text_branch == "cet":
+            if self.use_cet and (self.training or not self.use_prompt_memory_output):
+                from . import cet
+
+                encoded_text, loss_linear_adapter = cet.cet_apply(bert_hidden, encoded_text, self.cet_adapter, self.zero_loss_type,
+                                                                  self.use_zero_inter_loss)
+        elif self.side_branch == "multilayer":
             rep_out, loss_linear_adapter = self.rep_language_adapter(bert_hidden)
             encoded_text = rep_out + encoded_text
         elif self.use_cet:
@@ -847,7 +878,7 @@ class GroundingDINO(nn.Module):
                 loss_dict["loss_conv_adapter"] = loss_conv_adapter * self.loss_adapter_weight
                 total = None if total is None else total + loss_dict["loss_conv_adapter"].reshape(())
             if self.use_cet and self.use_zero_inter_loss:
-                key = "loss_language_adapter" if self.side_branch == "multilayer" else "loss_linear_adapter"
+                key = self._text_loss_name()
                 loss_dict[key] = loss_linear_adapter * self.loss_adapter_weight
                 total = None if total is None else total + loss_dict[key].reshape(())
             if self.use_cet and self.use_prompt_memory:       # weight 1 (groundingdino_dt.py:649-650)
@@ -1024,14 +1055,22 @@ class GroundingDINO(nn.Module):
         """Name prefixes of the parameters ``replay_memory``'s losses reach: the language side branch with its twin, and -- where
         their switches make them trainable -- the text encoder, ``feat_map`` and the pool entries."""
         branch = "rep_language_adapter." if self.side_branch == "multilayer" else "rep_linear_adapter."
+        if self.text_branch == "cet":
+            branch = "cet_adapter."
         return (branch, "bert.", "feat_map.", "prompt_memory_pool.")
+
+    def _text_loss_name(self):
+        """The loss dict's key of the text side's zero-interference term: the reference's name for the module that is built."""
+        if self.text_branch == "cet":
+            return "loss_adapter_text"
+        return "loss_language_adapter" if self.side_branch == "multilayer" else "loss_linear_adapter"
 
     def replay_memory(self):
         """One iteration's losses of the text-only replay stage (groundingdino_dt.py ``replay_memory`` :786-838; it takes no
         images): the captions of all learned classes are encoded -- feat_map + side branch -- and pulled back to the stored rows.
         Returns ``{"loss_prompt_memory": 0.5 * loss}`` and, with ``use_zero_inter_loss``, the side branch's zero-interference
         term times ``loss_adapter_weight`` under the key the training forward uses for it (``loss_linear_adapter`` /
-        ``loss_language_adapter``; the reference's name ``loss_adapter_text`` belongs to a module this class does not have).
+        ``loss_language_adapter``; with ``text_branch="cet"``, the module the reference's name belongs to, ``loss_adapter_text``).
 
         The captions are ``vocab.split_categories(learned_classes)``: J = 1 is the reference's single caption
         ``".".join(learned) + "."``; J > 1 -- a departure -- is this package's answer to lists longer than ``max_text_len``,
@@ -1064,8 +1103,7 @@ class GroundingDINO(nn.Module):
         text_dict, _, loss_linear_adapter = self.encode_text(captions, device, names_list=names_list, bert_hidden=hidden)
         losses = {"loss_prompt_memory": text_dict.pop("loss_prompt_memory") * 0.5}
         if self.use_zero_inter_loss:
-            name = "loss_language_adapter" if self.side_branch == "multilayer" else "loss_linear_adapter"
-            losses[name] = loss_linear_adapter.reshape(()) * self.loss_adapter_weight
+            losses[self._text_loss_name()] = loss_linear_adapter.reshape(()) * self.loss_adapter_weight
         return losses
 
     def side_branch_parameters(self):
@@ -1074,7 +1112,7 @@ class GroundingDINO(nn.Module):
 
 
 @MODULE_BUILD_FUNCS.registe_with_name(module_name="dualzerorepbranchgroundingdino")
-def build_dual_zero_rep_branch_groundingdino(args, bert=None, tokenizer=None, side_branch="rep"):
+def build_dual_zero_rep_branch_groundingdino(args, bert=None, tokenizer=None, side_branch="rep", **model_kw):
     backbone = build_backbone(args)
     transformer = build_transformer(args)
     criterion = build_criterion(args)
@@ -1095,11 +1133,38 @@ def build_dual_zero_rep_branch_groundingdino(args, bert=None, tokenizer=None, si
         use_cls_linear=args.use_cls_linear, use_prompt_tuning=args.use_prompt_tuning,
         use_prompt_memory_output=args.use_prompt_memory_output,
         use_project_tuning=getattr(args, "use_project_tuning", False),
-        use_project_adapter=args.use_project_adapter,
+        use_project_adapter=model_kw.pop("use_project_adapter", args.use_project_adapter),
         use_zero_inter_loss_for_conv=args.use_zero_inter_loss_for_conv,
         use_learned_names=args.use_learned_names, device=getattr(args, "device", "cuda"),
         bert=bert, tokenizer=tokenizer, side_branch=side_branch, use_adapter=getattr(args, "use_adapter", False),
-        use_self_kd=getattr(args, "use_self_kd", False))
+        use_self_kd=getattr(args, "use_self_kd", False), **model_kw)
+
+
+@MODULE_BUILD_FUNCS.registe_with_name(module_name="dtgroundingdino")
+def build_dt_groundingdino(args, bert=None, tokenizer=None):
+    """The CET text-adapter baseline (reference groundingdino_dt.py, builder :1036-1110, run with
+    ``GroundingDINO_SwinT_OGC_dt.py``): the same detector with ``text_branch="cet"`` -- ``use_cet`` builds ``cet_adapter``
+    (``args.cet_type``, ``args.cet_middle_dim``; defaults "Adapter" and 1024) in place of the language ``RepZeroLinear`` -- and no
+    vision side branches.  Departures from groundingdino_dt.py, all stated:
+
+    * the text side's zero-interference term stands in the loss dict under its own key, ``loss_adapter_text`` (the name the
+      reference's ``replay_memory`` gives it), times ``loss_adapter_weight``; the reference's training forward adds it to the
+      transformer's adapter loss and reports the sum as ``loss_adapter`` (:647-654).  ``loss_adapter`` here stays the
+      transformer's own, under ``use_adapter`` and ``use_self_kd``;
+    * ``use_project_adapter`` is off whatever ``args`` says: the dt class's optional branches beside the input projections are
+      plain convolutions with a GroupNorm (:256-279), modules this package does not build; its builder defaults to none;
+    * the memory loss is the L1 mean whatever ``zero_loss_type`` (the reference applies the selected ``adapter_loss`` to it as
+      well, :519); ``use_prompt_memory`` with another type raises;
+    * ``cet_type="Transformer"`` raises ``NotImplementedError``; ``load_state_dict`` does not re-run ``add_cls_prompt`` or the
+      freezing (:761-784): pool entries load as they are and ``before_train`` freezes, as in the class this package mirrors;
+    * denoising queries (``dn_number``) are off, as in every builder here, and ``inference`` / ``add_cls_prompt``'s eval path
+      (:840-1033) is this class's ordinary eval forward.
+
+    ``after_train`` has nothing to merge for ``cet_adapter``: its keys stay in the final checkpoint."""
+    return build_dual_zero_rep_branch_groundingdino(
+        args, bert=bert, tokenizer=tokenizer, text_branch="cet", cet_type=getattr(args, "cet_type", "Adapter"),
+        cet_middle_dim=getattr(args, "cet_middle_dim", 1024), zero_loss_type=getattr(args, "zero_loss_type", "L1"),
+        use_project_adapter=False)
 
 
 @MODULE_BUILD_FUNCS.registe_with_name(module_name="dualzerorepmultilayerbranchgroundingdino")
