@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/zira_msda.h, include/zira_metrics.h, include/zira_rsb_ml.h,
-include/zira_nms.h, include/zira_vocab.h, include/zira_lvis.h, include/zira_phrase.h, include/zira_adapter.h, include/zira_clslinear.h, include/zira_prompt.h, include/zira_prompt_memory.h and include/zira_cet.h, derived from the headers at import (_header.py).
+include/zira_nms.h, include/zira_vocab.h, include/zira_lvis.h, include/zira_phrase.h, include/zira_adapter.h, include/zira_clslinear.h, include/zira_prompt.h, include/zira_prompt_memory.h, include/zira_cet.h and include/zira_lora.h, derived from the headers at import (_header.py).
 
 There is deliberately no fallback: if ``libzira_msda.so`` is missing the import of the op
 raises, so a GPU box can never silently run a non-HIP path.
@@ -27,6 +27,7 @@ _CLSLINEAR_HEADER = os.path.join(_HERE, os.pardir, "include", "zira_clslinear.h"
 _PROMPT_HEADER = os.path.join(_HERE, os.pardir, "include", "zira_prompt.h")
 _PMEM_HEADER = os.path.join(_HERE, os.pardir, "include", "zira_prompt_memory.h")
 _CET_HEADER = os.path.join(_HERE, os.pardir, "include", "zira_cet.h")
+_LORA_HEADER = os.path.join(_HERE, os.pardir, "include", "zira_lora.h")
 # Structs whose arrays are rows of a device tensor (optim_tail.py, ema.py): callers pass ``data_ptr()``, a plain address, which
 # ``POINTER(struct)`` refuses, so their pointers are ``c_void_p``.  The others are host descriptors built with ctypes.
 DEVICE_TABLES = ("zira_optim_segment", "zira_ema_segment", "zira_prompt_segment")
@@ -86,6 +87,9 @@ PMEM_SYMBOLS = tuple(PMEM_PROTOTYPES)
 # The twelfth, the CET text adapter's (cet.py): prototypes and its limits and loss codes.
 CET_PROTOTYPES, _, CET_CONSTANTS = read_header(_CET_HEADER)
 CET_SYMBOLS = tuple(CET_PROTOTYPES)
+# The thirteenth, the low-rank language side branch's (rsb.py, RepZeroLoRA): prototypes and its limits.
+LORA_PROTOTYPES, _, LORA_CONSTANTS = read_header(_LORA_HEADER)
+LORA_SYMBOLS = tuple(LORA_PROTOTYPES)
 
 _lib = None
 
@@ -115,7 +119,7 @@ def load():
                                       + list(LVIS_PROTOTYPES.items()) + list(PHRASE_PROTOTYPES.items())
                                       + list(ADAPTER_PROTOTYPES.items()) + list(CLSLINEAR_PROTOTYPES.items())
                                       + list(PROMPT_PROTOTYPES.items()) + list(PMEM_PROTOTYPES.items())
-                                      + list(CET_PROTOTYPES.items())):
+                                      + list(CET_PROTOTYPES.items()) + list(LORA_PROTOTYPES.items())):
         f = getattr(lib, name)
         f.argtypes, f.restype = argtypes, restype
     _lib = lib

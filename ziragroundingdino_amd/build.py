@@ -13,13 +13,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libzira_msda.so")
 OBJ_DIR = os.path.join(_HERE, "csrc", "_obj")
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("msda.hip", "msda_cells.hip", "msda_tiles.hip", "msda_cpu.cpp", "rsb.hip", "rsb_ml.hip", "xty.hip", "xty_bf16x3.hip", "bisoftmax.hip", "layernorm.hip", "groupnorm.hip", "lsap.hip", "catlogits.hip", "winattn.hip", "refpoints.hip", "attn.hip", "sampling.hip", "gemm_drelu.hip", "rowgemm.hip", "gemm_bf16x3.hip", "gemm_f16x2.hip", "gemm_f16x2_panel.hip", "ffn_f16x2.hip", "thin_f16x2.hip", "criterion.hip", "textside.hip", "topk.hip", "grounding.hip", "optim_tail.hip", "ema.hip", "place.hip", "apmatch.hip", "resample.hip", "vocmatch.hip", "apaccum.hip", "metrics.hip", "nms.hip", "vocab.hip", "lvismatch.hip", "phrasematch.hip", "adapter.hip", "clslinear.hip", "prompt.hip", "prompt_memory.hip", "cet.hip")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("msda.hip", "msda_cells.hip", "msda_tiles.hip", "msda_cpu.cpp", "rsb.hip", "rsb_ml.hip", "xty.hip", "xty_bf16x3.hip", "bisoftmax.hip", "layernorm.hip", "groupnorm.hip", "lsap.hip", "catlogits.hip", "winattn.hip", "refpoints.hip", "attn.hip", "sampling.hip", "gemm_drelu.hip", "rowgemm.hip", "gemm_bf16x3.hip", "gemm_f16x2.hip", "gemm_f16x2_panel.hip", "ffn_f16x2.hip", "thin_f16x2.hip", "criterion.hip", "textside.hip", "topk.hip", "grounding.hip", "optim_tail.hip", "ema.hip", "place.hip", "apmatch.hip", "resample.hip", "vocmatch.hip", "apaccum.hip", "metrics.hip", "nms.hip", "vocab.hip", "lvismatch.hip", "phrasematch.hip", "adapter.hip", "clslinear.hip", "prompt.hip", "prompt_memory.hip", "cet.hip", "lora.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "zira_msda.h"), os.path.join(_ROOT, "include", "zira_metrics.h"),
            os.path.join(_ROOT, "include", "zira_rsb_ml.h"), os.path.join(_ROOT, "include", "zira_nms.h"),
            os.path.join(_ROOT, "include", "zira_vocab.h"), os.path.join(_ROOT, "include", "zira_lvis.h"),
            os.path.join(_ROOT, "include", "zira_phrase.h"), os.path.join(_ROOT, "include", "zira_adapter.h"),
            os.path.join(_ROOT, "include", "zira_clslinear.h"), os.path.join(_ROOT, "include", "zira_prompt.h"),
            os.path.join(_ROOT, "include", "zira_prompt_memory.h"), os.path.join(_ROOT, "include", "zira_cet.h"),
+           os.path.join(_ROOT, "include", "zira_lora.h"),
            os.path.join(_HERE, "csrc", "cat_max.h"), os.path.join(_HERE, "csrc", "prompt_table.h"),
            os.path.join(_HERE, "csrc", "msda_internal.h"),
            os.path.join(_HERE, "csrc", "msda_fwd_lean.h"), os.path.join(_HERE, "csrc", "split_arith.h"),

@@ -35,7 +35,7 @@ from .box_ops import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh
 from .criterion import build_criterion
 from .dense import conv_module_as_gemm
 from .graphs import GraphedNoGrad, GraphedTransformer
-from .rsb import RepZeroConv2d, RepZeroLinear
+from .rsb import RepZeroConv2d, RepZeroLinear, RepZeroLoRA
 from .structures import Boxes, ImageList, Instances
 from .text_masks import generate_masks_with_special_tokens_and_transfer_map
 from .transformer import build_transformer
@@ -91,7 +91,8 @@ class GroundingDINO(nn.Module):
                  use_project_tuning=False, use_project_adapter=True,
                  use_zero_inter_loss_for_conv=True, use_learned_names=False,
                  bert=None, tokenizer=None, side_branch="rep", use_adapter=False, use_self_kd=False,
-                 text_branch="rep", cet_type="Adapter", cet_middle_dim=1024, zero_loss_type="L1", **_unused):
+                 text_branch="rep", cet_type="Adapter", cet_middle_dim=1024, zero_loss_type="L1", lora_down_dim=None,
+                 **_unused):
         super().__init__()
         assert query_dim == 4 and iter_update, "GroundingDINO uses 4-d queries with iterative update"
         assert two_stage_type in ["no", "standard"]
@@ -130,8 +131,11 @@ class GroundingDINO(nn.Module):
         assert side_branch in ("rep", "multilayer")
         self.side_branch = side_branch
         # "rep": ZiRa's RepZeroLinear beside feat_map; "cet": the sibling class's trained text adapter in its place
-        # (groundingdino_dt.py:182-215, cet.py) -- ``use_cet`` then builds ``cet_adapter``, which nothing merges
-        assert text_branch in ("rep", "cet")
+        # (groundingdino_dt.py:182-215, cet.py) -- ``use_cet`` then builds ``cet_adapter``, which nothing merges; "lora": the
+        # low-rank form of ZiRa's branch under the same name (adapter.py:227-259, rsb.RepZeroLoRA), merged like the dense one
+        assert text_branch in ("rep", "cet", "lora")
+        if text_branch == "lora" and side_branch != "rep":
+            raise ValueError('text_branch="lora" goes with side_branch="rep": the multilayer ablation has a language branch of its own')
         if text_branch == "cet":
             from . import cet
 
@@ -153,6 +157,8 @@ class GroundingDINO(nn.Module):
             conv_branch = RepZeroConv2d
             if use_cet and text_branch == "cet":
                 self.cet_adapter = cet.build_cet_adapter(cet_type, self.bert.config.hidden_size, cet_middle_dim, hidden_dim)
+            elif use_cet and text_branch == "lora":
+                self.rep_linear_adapter = RepZeroLoRA(self.bert.config.hidden_size, hidden_dim, down_dim=lora_down_dim)
             elif use_cet:  # RSB #1: language side branch beside feat_map
                 self.rep_linear_adapter = RepZeroLinear(self.bert.config.hidden_size, hidden_dim)
         self.specical_tokens = self.tokenizer.convert_tokens_to_ids(["[CLS]", "[SEP]", ".", "?"])
@@ -1137,7 +1143,9 @@ def build_dual_zero_rep_branch_groundingdino(args, bert=None, tokenizer=None, si
         use_zero_inter_loss_for_conv=args.use_zero_inter_loss_for_conv,
         use_learned_names=args.use_learned_names, device=getattr(args, "device", "cuda"),
         bert=bert, tokenizer=tokenizer, side_branch=side_branch, use_adapter=getattr(args, "use_adapter", False),
-        use_self_kd=getattr(args, "use_self_kd", False), **model_kw)
+        use_self_kd=getattr(args, "use_self_kd", False),
+        text_branch=model_kw.pop("text_branch", getattr(args, "text_branch", "rep")),
+        lora_down_dim=getattr(args, "lora_down_dim", None), **model_kw)
 
 
 @MODULE_BUILD_FUNCS.registe_with_name(module_name="dtgroundingdino")

@@ -184,6 +184,7 @@ class Switches:
     native_prompt = True       # prompt.substitute (only with use_prompt_tuning): one autograd node over csrc/prompt.hip; off = prompt.substitute_reference
     native_prompt_memory = True   # prompt.memory_loss (only with use_prompt_memory): one autograd node over csrc/prompt_memory.hip; off = prompt.memory_loss_reference
     native_cet = True          # cet.cet_apply (only with text_branch="cet"): one autograd node over csrc/cet.hip; off = cet.cet_reference
+    native_lora = True         # rsb.lora_apply (only with text_branch="lora"): one autograd node over csrc/lora.hip; off = rsb.lora_reference
     native_ema = True          # ema.EMAUpdater.update / apply_and_restore: one launch over every fp32 CUDA tensor (csrc/ema.hip); off = the reference's op chain
     # arithmetic of the frozen FFN products on the image-token rows: "f32" = the library's fp32 GEMMs (+ csrc/gemm_drelu.hip);
     # "bf16x3" = fp32-accurate split-bf16 products on the bf16 matrix cores (csrc/gemm_bf16x3.hip, gemm_bf16x3.py);
