@@ -51,6 +51,8 @@ def kernels(root, mod, src, tmp, label):
             out[name] = []
             continue
         line = line.split("//")[0].strip()
+        if line == "...":        # objdump's mark for zero padding behind a symbol: it depends on what follows, not on the kernel
+            continue
         if name is not None and line:
             out[name].append(line)
     return out

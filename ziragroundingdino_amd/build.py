@@ -25,7 +25,8 @@ HEADERS = [os.path.join(_ROOT, "include", "zira_msda.h"), os.path.join(_ROOT, "i
            os.path.join(_HERE, "csrc", "msda_internal.h"),
            os.path.join(_HERE, "csrc", "msda_fwd_lean.h"), os.path.join(_HERE, "csrc", "split_arith.h"),
            os.path.join(_HERE, "csrc", "lane_sum.h"), os.path.join(_HERE, "csrc", "launch.h"),
-           os.path.join(_HERE, "csrc", "mfma_f32_tile.h"),
+           os.path.join(_HERE, "csrc", "mfma_f32_tile.h"), os.path.join(_HERE, "csrc", "ticket.h"),
+           os.path.join(_HERE, "csrc", "gate.h"), os.path.join(_HERE, "csrc", "zero_loss.h"),
            os.path.join(_HERE, "csrc", "stable_desc.h"), os.path.join(_HERE, "csrc", "topk_select.h")]
 HIPCC_FLAGS = [
     "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",

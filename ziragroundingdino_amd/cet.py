@@ -27,7 +27,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .adapter import gate_scale_reference
-from .dense import _scratch
+from .dense import _scratch, _zeroed_once
 
 FORCE_REFERENCE = False      # True: every call is cet_reference
 CET_TYPES = ("Adapter", "Linear", "Transformer")
@@ -129,21 +129,8 @@ def _check(rc, name):
 
 
 def _tickets(dev, words):
-    """The forward's ticket words on ``dev``: allocated ZEROED once, outside any capture -- every forward leaves them at zero
-    again, so neither a later call nor a graph replay clears them.  One buffer serves one stream at a time: an eager call on
-    another stream than the last one first waits for that stream."""
-    held = _TICKETS.get(dev)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if held is None or held[0].numel() < words:
-        if capturing:
-            raise RuntimeError("cet.cet_apply: no ticket words on %s yet; run once outside the capture first" % (dev,))
-        held = _TICKETS[dev] = [torch.zeros(max(words, MAX_ROWS // 32 + 4), dtype=torch.int32, device=dev), None]
-    if not capturing:
-        stream = torch.cuda.current_stream(dev)
-        if held[1] is not None and held[1] != stream:
-            stream.wait_stream(held[1])
-        held[1] = stream
-    return held[0]
+    """The forward's ticket words on ``dev`` (``dense._zeroed_once``)."""
+    return _zeroed_once(_TICKETS, dev, words, torch.int32, MAX_ROWS // 32 + 4, "cet.cet_apply: no ticket words on %s")
 
 
 def native_supported(x: Tensor, feat: Tensor, module) -> bool:

@@ -19,6 +19,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gate.h"
+#include "launch.h"
 #include "mfma_f32_tile.h"
 #include "zira_adapter.h"
 #include "zira_msda.h"
@@ -32,6 +34,7 @@ constexpr int kPS = kWaveRows + 1;                   // LDS stride of the row-do
 constexpr int kWavePart = kD + kMaxG * kD;           // g_b_up, g_gate: floats a wave carries out of the row-major pass
 constexpr int kBwdPart = kH + kWavePart;             // doubles a block leaves: g_b_down, g_b_up, g_gate
 constexpr long long kMaxM = 1ll << 22;
+using zira::align4, zira::misaligned;
 
 // gs[g][:] = gate[g] / |gate[g]| for g < G, zeros above; ginv[g] = 1 / |gate[g]|.  Wave w takes rows w and w + 4.
 __device__ __forceinline__ void normalise_gate(const float *__restrict__ gate, int G, float *gs, float *ginv, int wave, int lane)
@@ -137,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void adapter_fwd(const float *__restrict_
     if (self_kd) {
         double s = row < M ? (double)ab_half : 0.0;
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);      // (lane_sum.h's lane_sum_xor64, inline: the call is other code)
         if (lane == 0) wsum[wave] = s;
     }
 
@@ -185,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void adapter_fwd(const float *__restrict_
         if (blockIdx.x == 0 && tid == 0) loss[0] = 0.f;
         return;
     }
-    if (tid == 0) {
+    if (tid == 0) {      // (ticket.h's protocol in its older spelling: __threadfence() and atomic loads are other machine code)
         part[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
         __threadfence();
         const unsigned ticket = atomicInc(counter, gridDim.x - 1);       // wraps to 0 behind the last block: ready for the next call
@@ -307,16 +310,11 @@ __global__ __launch_bounds__(kThreads) void adapter_bwd_rows(const float *__rest
 #pragma unroll
         for (int i = 0; i < 32; ++i) dot += dots[r * kPS + i];
         const float g_s = dot + gb;
-        float a = 0.f, b = 0.f, al = 0.f, be = 0.f;
-        if (G > 0) {
-            const float g_c = g_s * gate_T * sc_r * (1.f - sc_r / base), gi = ginv[id_r];
-            a = g_c * rn_r;
-            b = -(g_c * c_r) * rn_r * rn_r;
-            al = g_c * rn_r * gi;
-            be = -(g_c * c_r) * gi;
-        }
+        GateCoeffs co = {0.f, 0.f, 0.f, 0.f};
+        if (G > 0) co = gate_backward_coeffs(g_s * gate_T * sc_r * (1.f - sc_r / base), c_r, rn_r, ginv[id_r]);
         if (hh == 0) {
-            coef[wave][r][0] = a; coef[wave][r][1] = b; coef[wave][r][2] = al; coef[wave][r][3] = be; coef[wave][r][4] = sc_r;
+            coef[wave][r][0] = co.a; coef[wave][r][1] = co.b; coef[wave][r][2] = co.alpha; coef[wave][r][3] = co.beta;
+            coef[wave][r][4] = sc_r;
             idrow[wave][r] = G > 0 ? id_r : 0;
         }
     }
@@ -389,6 +387,7 @@ __global__ __launch_bounds__(kThreads) void adapter_bwd_rows(const float *__rest
                        + (double)scratch[3 * kWavePart + e];
 }
 
+// (the structure of cet_bwd_fold; one kernel template for both came out as other machine code)
 // out element e < n_out: the sum over the blocks' doubles in index order.  A block folds 16 elements: 16 groups of threads each
 // add every 16th block's partial, LDS joins the groups in a fixed order.  e: [0, 64) g_b_down, [64, 320) g_b_up, the rest g_gate.
 __global__ __launch_bounds__(kThreads) void adapter_bwd_fold(const double *__restrict__ part, int nblocks, int n_out,
@@ -410,7 +409,6 @@ __global__ __launch_bounds__(kThreads) void adapter_bwd_fold(const double *__res
     }
 }
 
-inline size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
 inline size_t blocks_of(long long M) { return (size_t)((M + kPanel - 1) / kPanel); }
 
 // workspace (floats): [the blocks' doubles: max(1, kBwdPart) per block][gh M x 64][scale * h M x 64][zira_xty_f32's scratch]
@@ -424,12 +422,9 @@ inline Layout layout(long long M)
     l.gh = align4(2 * blocks_of(M) * kBwdPart);
     l.sh = l.gh + (size_t)M * kH;
     l.xty = l.sh + (size_t)M * kH;
-    const size_t a = zira_xty_workspace_floats(1, (int)M, kH, kD), b = zira_xty_workspace_floats(1, (int)M, kD, kH);
-    l.total = l.xty + align4(a > b ? a : b);
+    l.total = l.xty + align4(zira::max_xty_workspace(M, {{kH, kD}, {kD, kH}}));
     return l;
 }
-
-inline bool misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }
 
 }  // namespace
 

@@ -14,7 +14,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gate.h"
+#include "launch.h"
 #include "mfma_f32_tile.h"
+#include "ticket.h"
+#include "zero_loss.h"
 #include "zira_cet.h"
 #include "zira_msda.h"
 
@@ -26,26 +30,7 @@ constexpr int kFill = 512;                           // waves the forward and th
 constexpr int kPrepWaves = 4, kPrepThreads = 64 * kPrepWaves, kPrepRows = kTileRows / kPrepWaves;
 constexpr int kGateSlots = kMaxE / 64;               // columns of x a lane of the row pass holds
 constexpr int kFoldThreads = 256;
-
-__device__ __forceinline__ void release_agent()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-__device__ __forceinline__ void acquire_agent()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// lane 0 draws a ticket of a word that wraps behind `last`; every lane learns whether it was the last one
-__device__ __forceinline__ bool drew_last(unsigned *word, unsigned last, int lane)
-{
-    unsigned t = 0;
-    if (lane == 0) t = atomicInc(word, last);
-    return (unsigned)__builtin_amdgcn_readfirstlane((int)t) == last;
-}
+using zira::align4, zira::misaligned, zira::tiles_of;
 
 // gs[g][:] = gate[g] / |gate[g]|, ginv[g] = 1 / |gate[g]| for g < G.  Wave `wave` of `nwaves` takes rows wave, wave + nwaves, ...
 __device__ __forceinline__ void normalise_gate(const float *__restrict__ gate, int G, int E, float *gs, float *ginv, int wave,
@@ -102,8 +87,7 @@ __device__ __forceinline__ f32x16 hidden_of(const f32x16 &a0, const f32x16 &a1, 
     return hv;
 }
 
-__device__ __forceinline__ float sign_of(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-
+// (zero_loss.h's SmoothL1 beside L1 and L2 under one switch, |o| taken once ahead of it: calling into the header is other code)
 __device__ __forceinline__ float loss_of(float o, int loss_type)
 {
     const float a = fabsf(o);
@@ -199,13 +183,8 @@ __global__ __launch_bounds__(64) void cet_fwd(const float *__restrict__ x, const
         const f32x16 hv = hidden_of(a0, a1, bd, hid0, hh);
 #pragma unroll
         for (int j = 0; j < kOutTiles; ++j) {
-            const float *wu = Wu + (size_t)(32 * j + r) * H + hid0 + 4 * hh;
-            float wa[16];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 w = *reinterpret_cast<const float4 *>(wu + 8 * q);
-                wa[4 * q] = w.x; wa[4 * q + 1] = w.y; wa[4 * q + 2] = w.z; wa[4 * q + 3] = w.w;
-            }
+            float wa[16];                                        // W_u[32 j + r] at the hidden units of hv's registers
+            load_tile(Wu + (size_t)(32 * j + r) * H, hid0, hh, wa);
             mfma_chain<16>(wa, hv, o[j]);
         }
     }
@@ -214,15 +193,12 @@ __global__ __launch_bounds__(64) void cet_fwd(const float *__restrict__ x, const
     if (S > 1) {
         float *mine = part_out + ((size_t)(s * tiles + tile) * kTileRows + r) * kOut;
 #pragma unroll
-        for (int j = 0; j < kOutTiles; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                *reinterpret_cast<float4 *>(mine + 32 * j + 8 * q + 4 * hh) =
-                    make_float4(o[j][4 * q], o[j][4 * q + 1], o[j][4 * q + 2], o[j][4 * q + 3]);
+        for (int j = 0; j < kOutTiles; ++j) store_tile(mine, 32 * j, hh, o[j]);
         release_agent();
         if (!drew_last(tickets + 1 + tile, (unsigned)S - 1, lane)) return;
         acquire_agent();
         scale = scale_out[rowc];
+        // (load_tile's map a quad at a time, one loop over the S partials per 16-byte access: a whole tile per loop is other code)
 #pragma unroll
         for (int j = 0; j < kOutTiles; ++j)
 #pragma unroll
@@ -262,7 +238,7 @@ __global__ __launch_bounds__(64) void cet_fwd(const float *__restrict__ x, const
         return;
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
+    for (int off = 32; off >= 1; off >>= 1) lsum += __shfl_xor(lsum, off, 64);      // (lane_sum_xor64, inline: the call is other code)
     if (lane == 0) part_loss[tile] = lsum;
     release_agent();
     if (!drew_last(tickets, (unsigned)tiles - 1, lane)) return;
@@ -322,14 +298,14 @@ __global__ __launch_bounds__(kPrepThreads) void cet_bwd_prep(const float *__rest
             int id = __builtin_amdgcn_readfirstlane(amax[row]);
             id = id < 0 ? 0 : (id >= G ? G - 1 : id);
             const float g_c = (dot / sc) * gate_T * sc * (1.f - sc / base), rn = rnorm[row], c = cosv[row], gi = ginv[id];
-            const float a = g_c * rn, b = -(g_c * c) * rn * rn, al = g_c * rn * gi, be = -(g_c * c) * gi;
+            const GateCoeffs co = gate_backward_coeffs(g_c, c, rn, gi);
 #pragma unroll
             for (int m = 0; m < kGateSlots; ++m) {
                 const int k = lane + 64 * m;
                 if (k < E) {
                     const float xv = x[(size_t)row * E + k], gv = gs[id * E + k];
-                    if (gx != nullptr) gx[(size_t)row * E + k] = fmaf(a, gv, b * xv);
-                    const float d = fmaf(al, xv, be * gv);
+                    if (gx != nullptr) gx[(size_t)row * E + k] = fmaf(co.a, gv, co.b * xv);
+                    const float d = fmaf(co.alpha, xv, co.beta * gv);
 #pragma unroll
                     for (int g = 0; g < kMaxG; ++g)
                         if (id == g) gg[g][m] += d;
@@ -380,6 +356,7 @@ __global__ __launch_bounds__(64) void cet_bwd_hidden(const float *__restrict__ x
         f32x16 a0 = zero16(), a1 = zero16();
         down_panel(xrow, Wd + (size_t)(hid0 + r) * E, E, hh, a0, a1);
         const f32x16 hv = hidden_of(a0, a1, bd, hid0, hh);
+        // (g_h^T = W_u^T g^T as in lora_bwd_gh, and store_tile's map a quad at a time: shared spellings are other machine code)
         f32x16 g0 = zero16(), g1 = zero16();
 #pragma unroll
         for (int c = 0; c < kOut / 32; ++c) {
@@ -442,6 +419,7 @@ __global__ __launch_bounds__(64) void cet_bwd_gx(const float *__restrict__ gh, c
     }
 }
 
+// (the structure of adapter_bwd_fold; one kernel template for both came out as other machine code)
 // element e of [g_b_up 256 | g_gate G * E | g_b_down H]: the sum over the tiles' doubles in index order.  A block folds 16
 // elements: 16 groups of threads each add every 16th tile's partial, LDS joins the groups in a fixed order.
 __global__ __launch_bounds__(kFoldThreads) void cet_bwd_fold(const double *__restrict__ part1, const double *__restrict__ part2,
@@ -466,10 +444,6 @@ __global__ __launch_bounds__(kFoldThreads) void cet_bwd_fold(const double *__res
     }
 }
 
-inline size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
-inline int tiles_of(long long M) { return (int)((M + kTileRows - 1) / kTileRows); }
-inline bool misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }
-
 inline bool shape_ok(long long M, int E, int H, int G)
 {
     return M >= 1 && M <= ZIRA_CET_MAX_ROWS && E >= 32 && E <= kMaxE && E % 32 == 0 && H >= 32 && H <= kMaxH && H % 32 == 0
@@ -478,7 +452,7 @@ inline bool shape_ok(long long M, int E, int H, int G)
 
 inline int splits_of(long long M, int H)
 {
-    int S = kFill / tiles_of(M);
+    int S = kFill / tiles_of(M, kTileRows);
     if (S < 1) S = 1;
     return S > H / 32 ? H / 32 : S;
 }
@@ -490,12 +464,11 @@ struct BwdLayout {
 inline BwdLayout bwd_layout(long long M, int E, int H, int G)
 {
     BwdLayout l;
-    const size_t tiles = (size_t)tiles_of(M);
+    const size_t tiles = (size_t)tiles_of(M, kTileRows);
     l.part1 = 0;
     l.part2 = align4(2 * tiles * (size_t)(kOut + G * E));
     l.xty = l.part2 + align4(2 * tiles * (size_t)H);
-    const size_t a = zira_xty_workspace_floats(1, (int)M, H, E), b = zira_xty_workspace_floats(1, (int)M, kOut, H);
-    l.total = l.xty + align4(a > b ? a : b);
+    l.total = l.xty + align4(zira::max_xty_workspace(M, {{H, E}, {kOut, H}}));
     return l;
 }
 
@@ -514,13 +487,13 @@ int zira_cet_splits(long long M, int H)
 size_t zira_cet_ticket_words(long long M)
 {
     if (M < 1 || M > ZIRA_CET_MAX_ROWS) return 0;
-    return align4(1 + (size_t)tiles_of(M));
+    return align4(1 + (size_t)tiles_of(M, kTileRows));
 }
 
 size_t zira_cet_fwd_workspace_floats(long long M, int H)
 {
     if (!shape_ok(M, 32, H, 0)) return 0;
-    const size_t tiles = (size_t)tiles_of(M), S = (size_t)splits_of(M, H);
+    const size_t tiles = (size_t)tiles_of(M, kTileRows), S = (size_t)splits_of(M, H);
     return align4(2 * tiles) + (S > 1 ? S * tiles * kTileRows * kOut : 0);
 }
 
@@ -541,7 +514,7 @@ int zira_cet_fwd_f32(const float *x, const float *feat, const float *w_down, con
         || !workspace || !tickets) return -1;
     if (misaligned(x) || misaligned(feat) || misaligned(w_down) || misaligned(b_down) || misaligned(w_up) || misaligned(b_up)
         || misaligned(gate) || misaligned(enc) || misaligned(out) || misaligned(workspace) || misaligned(tickets)) return -1;
-    const int tiles = tiles_of(M), S = splits_of(M, H);
+    const int tiles = tiles_of(M, kTileRows), S = splits_of(M, H);
     double *part_loss = reinterpret_cast<double *>(workspace);
     float *part_out = workspace + align4(2 * (size_t)tiles);
     const double inv_n = 1.0 / ((double)M * (double)kOut);
@@ -565,7 +538,7 @@ int zira_cet_bwd_f32(const float *grad_enc, const float *grad_loss, const float 
         || misaligned(gate) || misaligned(h) || misaligned(gh) || misaligned(gu) || misaligned(gx) || misaligned(g_w_down)
         || misaligned(g_w_up) || misaligned(workspace)) return -1;
     const BwdLayout l = bwd_layout(M, E, H, G);
-    const int tiles = tiles_of(M), S = splits_of(M, H), n1 = kOut + G * E;
+    const int tiles = tiles_of(M, kTileRows), S = splits_of(M, H), n1 = kOut + G * E;
     double *part1 = reinterpret_cast<double *>(workspace + l.part1), *part2 = reinterpret_cast<double *>(workspace + l.part2);
     float *xws = workspace + l.xty;
     hipStream_t st = (hipStream_t)stream;

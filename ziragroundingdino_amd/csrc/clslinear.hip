@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "cat_max.h"
+#include "launch.h"
 #include "mfma_f32_tile.h"
 #include "zira_clslinear.h"
 #include "zira_msda.h"
@@ -31,6 +32,7 @@ namespace {
 
 constexpr int kD = 256, kTiles = kD / 32, kRows = 32, kThreads = 64, kMaxT = 256, kMaxC = 256;
 constexpr long long kMaxR = 1ll << 22;
+using zira::align4, zira::misaligned;
 
 // the wave's place: block -> (prediction set and image, block of 32 queries)
 struct Place {
@@ -190,11 +192,7 @@ __global__ __launch_bounds__(kThreads) void cls_linear_bwd(const float *__restri
     }
     if (valid) {
 #pragma unroll
-        for (int j = 0; j < kTiles; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4 *>(gz + (size_t)row * kD + 32 * j + 8 * g + 4 * hh) =
-                    make_float4(acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3]);
+        for (int j = 0; j < kTiles; ++j) store_tile(gz + (size_t)row * kD, 32 * j, hh, acc[j]);
     }
 
     // ---- the block's column sums of gz, one double each ---------------------------------------------------------------------------------
@@ -220,16 +218,12 @@ __global__ __launch_bounds__(kThreads) void cls_linear_bwd(const float *__restri
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg)
                     o = __builtin_amdgcn_mfma_f32_32x32x2f32(wc[(size_t)(32 * j + rowmap(reg, hh)) * kD], acc[j][reg], o, 0, 0, 0);
-            if (valid) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<float4 *>(gx + (size_t)row * kD + 32 * kt + 8 * g + 4 * hh) =
-                        make_float4(o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]);
-            }
+            if (valid) store_tile(gx + (size_t)row * kD, 32 * kt, hh, o);
         }
     }
 
     // ---- g_b: the last block to arrive adds the blocks' doubles in index order ------------------------------------------------------------
+    // (ticket.h's protocol in its older spelling: __threadfence() is a stronger fence, other machine code)
     __threadfence();
     __syncthreads();
     if (lane == 0) {
@@ -252,7 +246,6 @@ __global__ __launch_bounds__(kThreads) void cls_linear_bwd(const float *__restri
     *reinterpret_cast<float4 *>(g_b + 4 * lane) = make_float4((float)s0, (float)s1, (float)s2, (float)s3);
 }
 
-inline size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
 inline long long blocks_of(long long R, int Q) { return (R / Q) * ((Q + kRows - 1) / kRows); }
 inline long long max_blocks(long long R) { return R; }      // (Q = 1: a block per row)
 
@@ -270,7 +263,6 @@ inline Layout layout(long long R)
     return l;
 }
 
-inline bool misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }
 inline bool bad_shape(long long R, int B, int Q, int T, int T_out, int Cmax)
 {
     return R < 1 || R > kMaxR || B < 1 || Q < 1 || R % ((long long)B * Q) != 0 || T < 1 || T > kMaxT || Cmax < 1 || Cmax > kMaxC

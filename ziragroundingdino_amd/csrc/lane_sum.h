@@ -71,6 +71,16 @@ __device__ __forceinline__ double lane_sum(double x)
     return x;
 }
 
+// The wave's 64 doubles by the plain `__shfl_xor` butterfly, offsets 32 ... 1.  It stands beside lane_sum<64> because it adds
+// in ANOTHER order (far partners first, neighbours last), and the order of the additions is part of the bits that the tests
+// of its users pin: the side-branch nodes' loss and gradient sums were written with it and keep it.
+__device__ __forceinline__ double lane_sum_xor64(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
 }  // namespace
 
 #endif  // ZIRA_LANE_SUM_H_

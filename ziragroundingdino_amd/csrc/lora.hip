@@ -14,7 +14,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "lane_sum.h"
+#include "launch.h"
 #include "mfma_f32_tile.h"
+#include "ticket.h"
+#include "zero_loss.h"
 #include "zira_lora.h"
 #include "zira_msda.h"
 
@@ -24,54 +28,7 @@ constexpr int kOut = ZIRA_LORA_OUT, kMaxE = ZIRA_LORA_MAX_E, kMaxR = ZIRA_LORA_M
 constexpr int kTileRows = 32, kOutTiles = kOut / 32;
 constexpr int kFill = 256;                           // waves the forward aims for
 constexpr int kFoldThreads = 256;
-
-__device__ __forceinline__ void release_agent()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-__device__ __forceinline__ void acquire_agent()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// lane 0 draws a ticket of a word that wraps behind `last`; every lane learns whether it was the last one
-__device__ __forceinline__ bool drew_last(unsigned *word, unsigned last, int lane)
-{
-    unsigned t = 0;
-    if (lane == 0) t = atomicInc(word, last);
-    return (unsigned)__builtin_amdgcn_readfirstlane((int)t) == last;
-}
-
-__device__ __forceinline__ float sign_of(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-__device__ __forceinline__ float sl1(float v) { const float a = fabsf(v); return a < 1.f ? 0.5f * v * v : a - 0.5f; }
-__device__ __forceinline__ float sl1_slope(float v) { return fabsf(v) < 1.f ? v : sign_of(v); }
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// registers 4 q ... 4 q + 3 of a transposed tile <-> four consecutive columns col0 + 8 q + 4 hh ... of the lane's row
-__device__ __forceinline__ void store_tile(float *rowp, int col0, int hh, const f32x16 &a)
-{
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<float4 *>(rowp + col0 + 8 * q + 4 * hh) = make_float4(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
-}
-
-__device__ __forceinline__ void load_tile(const float *rowp, int col0, int hh, f32x16 &a)
-{
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4 *>(rowp + col0 + 8 * q + 4 * hh);
-        a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-    }
-}
+using zira::align4, zira::misaligned, zira::tiles_of;
 
 // the S partial tiles at column col0 of row (tile, r), added in index order
 __device__ __forceinline__ f32x16 summed_tile(const float *part, int col0, int W, int S, int tiles, int tile, int r, int hh)
@@ -178,14 +135,14 @@ __global__ __launch_bounds__(64) void lora_fwd(const float *__restrict__ x, cons
             const float b = sc * o[e];
             v[e] = b + ta[j][e];
             if (row < M) {
-                sum_b += (double)sl1(b);
-                sum_o += (double)sl1(v[e]);
+                sum_b += (double)smooth_l1_zero(b);
+                sum_o += (double)smooth_l1_zero(v[e]);
             }
         }
         if (row < M) store_tile(out + (size_t)row * kOut, 32 * j, hh, v);
     }
-    sum_b = wave_sum(sum_b);
-    sum_o = wave_sum(sum_o);
+    sum_b = lane_sum_xor64(sum_b);
+    sum_o = lane_sum_xor64(sum_o);
     if (lane == 0) {
         part_loss[2 * tile] = sum_b;
         part_loss[2 * tile + 1] = sum_o;
@@ -245,7 +202,7 @@ __global__ __launch_bounds__(64) void lora_bwd_rows(const float *__restrict__ g_
     double gs = 0.0;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const float so = sl1_slope(ov[e]), sb = sl1_slope(sc * o[e]);
+        const float so = smooth_l1_zero_slope(ov[e]), sb = smooth_l1_zero_slope(sc * o[e]);
         const float t = go[e] + s * so;
         const float p = t + s * sb;
         vt[e] = t;
@@ -256,7 +213,7 @@ __global__ __launch_bounds__(64) void lora_bwd_rows(const float *__restrict__ g_
         store_tile(gt + (size_t)row * kOut, 32 * j, hh, vt);
         store_tile(gb + (size_t)row * kOut, 32 * j, hh, vb);
     }
-    gs = wave_sum(gs);
+    gs = lane_sum_xor64(gs);
     if (lane == 0) part[(size_t)tile * kOutTiles + j] = gs;
 }
 
@@ -268,6 +225,7 @@ __global__ __launch_bounds__(64) void lora_bwd_gh(const float *__restrict__ gb, 
     const int tile = blockIdx.x, hid0 = 32 * (int)blockIdx.y;
     const int row = tile * kTileRows + r, rowc = row < M ? row : M - 1;
     const float *grow = gb + (size_t)rowc * kOut;
+    // (the same body as the middle of cet_bwd_hidden; as one function the compiler commutes its address multiplies)
     f32x16 g0 = zero16(), g1 = zero16();
 #pragma unroll
     for (int c = 0; c < kOut / 32; ++c) {
@@ -329,10 +287,6 @@ __global__ __launch_bounds__(kFoldThreads) void lora_bwd_fold(const double *__re
     }
 }
 
-inline size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
-inline int tiles_of(long long M) { return (int)((M + kTileRows - 1) / kTileRows); }
-inline bool misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }
-
 inline bool shape_ok(long long M, int E, int R)
 {
     return M >= 1 && M <= ZIRA_LORA_MAX_ROWS && E >= 32 && E <= kMaxE && E % 32 == 0 && R >= 32 && R <= kMaxR && R % 32 == 0;
@@ -342,7 +296,7 @@ inline bool shape_ok(long long M, int E, int R)
 inline int panels_per_wave(long long M, int E)
 {
     const int np = E / 32;
-    int smax = kFill / tiles_of(M);
+    int smax = kFill / tiles_of(M, kTileRows);
     smax = smax < 1 ? 1 : (smax > np ? np : smax);
     return (np + smax - 1) / smax;
 }
@@ -359,10 +313,8 @@ struct BwdLayout {
 inline BwdLayout bwd_layout(long long M, int E, int R)
 {
     BwdLayout l;
-    l.xty = align4(2 * (size_t)tiles_of(M) * kOutTiles);
-    const size_t a = zira_xty_workspace_floats(1, (int)M, kOut, E), b = zira_xty_workspace_floats(1, (int)M, R, E),
-                 c = zira_xty_workspace_floats(1, (int)M, kOut, R);
-    l.total = l.xty + align4(a > b ? (a > c ? a : c) : (b > c ? b : c));
+    l.xty = align4(2 * (size_t)tiles_of(M, kTileRows) * kOutTiles);
+    l.total = l.xty + align4(zira::max_xty_workspace(M, {{kOut, E}, {R, E}, {kOut, R}}));
     return l;
 }
 
@@ -370,7 +322,7 @@ template <int HP>
 int launch_fwd(const float *x, const float *wd, const float *wu, const float *wt, const float *scaling, int M, int E, float *out,
                float *loss, float *h, float *workspace, uint32_t *tickets, hipStream_t st)
 {
-    const int tiles = tiles_of(M), S = splits_of(M, E), per = panels_per_wave(M, E);
+    const int tiles = tiles_of(M, kTileRows), S = splits_of(M, E), per = panels_per_wave(M, E);
     double *part_loss = reinterpret_cast<double *>(workspace);
     float *part = workspace + align4(4 * (size_t)tiles);
     hipLaunchKernelGGL(lora_fwd<HP>, dim3((unsigned)tiles, (unsigned)S), dim3(64), 0, st, x, wd, wu, wt, scaling, M, E, S, per,
@@ -384,8 +336,8 @@ int launch_bwd_rows(const float *g_out, const float *g_loss, const float *out, c
 {
     // ATen's mean backward divides by a host scalar: on the device that is a product with the fp32 reciprocal
     const float inv_n = 1.0f / (float)((long long)M * kOut);
-    hipLaunchKernelGGL(lora_bwd_rows<HP>, dim3((unsigned)tiles_of(M), (unsigned)kOutTiles), dim3(64), 0, st, g_out, g_loss, out, h,
-                       wu, scaling, M, inv_n, gb, gt, part);
+    hipLaunchKernelGGL(lora_bwd_rows<HP>, dim3((unsigned)tiles_of(M, kTileRows), (unsigned)kOutTiles), dim3(64), 0, st, g_out,
+                       g_loss, out, h, wu, scaling, M, inv_n, gb, gt, part);
     return (int)hipGetLastError();
 }
 
@@ -430,13 +382,13 @@ int zira_lora_splits(long long M, int E)
 size_t zira_lora_ticket_words(long long M)
 {
     if (M < 1 || M > ZIRA_LORA_MAX_ROWS) return 0;
-    return align4(1 + (size_t)tiles_of(M));
+    return align4(1 + (size_t)tiles_of(M, kTileRows));
 }
 
 size_t zira_lora_fwd_workspace_floats(long long M, int E, int R)
 {
     if (!shape_ok(M, E, R)) return 0;
-    const size_t tiles = (size_t)tiles_of(M), S = (size_t)splits_of(M, E);
+    const size_t tiles = (size_t)tiles_of(M, kTileRows), S = (size_t)splits_of(M, E);
     return align4(4 * tiles) + (S > 1 ? S * tiles * kTileRows * (size_t)(R + kOut) : 0);
 }
 
@@ -469,7 +421,7 @@ int zira_lora_bwd_f32(const float *grad_out, const float *grad_loss, const float
         || misaligned(w_twin) || misaligned(gb) || misaligned(gt) || misaligned(gh) || misaligned(gx) || misaligned(g_w_down)
         || misaligned(g_w_up) || misaligned(g_w_twin) || misaligned(workspace)) return -1;
     const BwdLayout l = bwd_layout(M, E, R);
-    const int tiles = tiles_of(M);
+    const int tiles = tiles_of(M, kTileRows);
     double *part = reinterpret_cast<double *>(workspace);
     float *xws = workspace + l.xty;
     hipStream_t st = (hipStream_t)stream;

@@ -56,6 +56,26 @@ __device__ __forceinline__ void mfma_chain(const A &a, const B &b, f32x16 &acc)
     for (int t = 0; t < N; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc, 0, 0, 0);
 }
 
+// rowmap's column-wise twin, for a tile kept TRANSPOSED (the lane's row r = lane & 31 of the matrix on the lane, 16 of the row's
+// 32 columns in its registers): registers 4 q ... 4 q + 3 <-> the four consecutive columns col0 + 8 q + 4 hh ... of the lane's
+// row, one 16-byte access each.  rowp: the lane's row, 16-byte aligned at col0
+__device__ __forceinline__ void store_tile(float *rowp, int col0, int hh, const f32x16 &a)
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        *reinterpret_cast<float4 *>(rowp + col0 + 8 * q + 4 * hh) = make_float4(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
+}
+
+template <typename A>      // (an f32x16 or a register array)
+__device__ __forceinline__ void load_tile(const float *rowp, int col0, int hh, A &a)
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 v = *reinterpret_cast<const float4 *>(rowp + col0 + 8 * q + 4 * hh);
+        a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
+    }
+}
+
 }  // namespace
 
 #endif  // ZIRA_MFMA_F32_TILE_H_

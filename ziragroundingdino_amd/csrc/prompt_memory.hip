@@ -18,16 +18,16 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "prompt_table.h"
+#include "ticket.h"
+#include "zero_loss.h"
 #include "zira_prompt.h"
 #include "zira_prompt_memory.h"
-#include "prompt_table.h"
 
 namespace {
 
 using namespace prompt_table;      // kThreads, kWave, kWavesPerBlock, f4, pool_row_of, aligned*, blocks_of
 constexpr size_t kTicketBytes = 16;      // the workspace's head: the ticket word, padded so that the doubles stay aligned
-
-__device__ __forceinline__ float sign_of(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }      // sgn(NaN) = 0, as ATen's
 
 __global__ __launch_bounds__(kThreads) void pmem_fwd_kernel(const float *__restrict__ x, const int32_t *__restrict__ table,
                                                             const zira_prompt_segment *__restrict__ segments, int n_pos, int D,
@@ -53,21 +53,19 @@ __global__ __launch_bounds__(kThreads) void pmem_fwd_kernel(const float *__restr
             }
         }
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+    for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);      // (lane_sum.h's lane_sum_xor64, inline)
     if (lane == 0) wave_sum[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int w = 0; w < kWavesPerBlock; ++w) s += wave_sum[w];
         part[blockIdx.x] = s;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        release_agent();
         is_last = atomicInc(ticket, gridDim.x - 1) == gridDim.x - 1;      // wraps to 0 behind the last block: ready for the next call
     }
     __syncthreads();
     if (!is_last || threadIdx.x != 0) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    acquire_agent();
     // (behind the acquire fence plain loads see the other blocks' doubles, and unlike atomic loads they are issued ahead of
     //  their use)
     double total = 0.0;

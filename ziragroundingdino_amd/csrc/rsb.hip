@@ -18,6 +18,8 @@
 #include <stdint.h>
 
 #include "lane_sum.h"
+#include "launch.h"
+#include "zero_loss.h"
 #include "zira_msda.h"
 
 namespace {
@@ -25,16 +27,11 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;  // 256 CUs x 8; grid-stride beyond
 
-__device__ __forceinline__ float smooth_l1_zero(float t)
-{
-    const float a = fabsf(t);
-    return a < 1.f ? 0.5f * t * t : a - 0.5f;
-}
+// (zero_loss.h's smooth_l1_zero_slope but for a NaN, which this one sends to -1: other behaviour, so it keeps its spelling)
 __device__ __forceinline__ float smooth_l1_zero_grad(float t)
 {
     return fabsf(t) < 1.f ? t : (t > 0.f ? 1.f : -1.f);
 }
-
 
 // block-wide sum of up to 3 values -> thread 0 writes them to dst[0..NV)
 template <int NV>
@@ -166,8 +163,6 @@ inline int rsb_grid(size_t n)
     return (int)blocks;
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -182,7 +177,7 @@ int zira_rsb_fwd_f32(const float *y_branch, const float *y_twin, const float *sc
                      float *out, float *loss, float *workspace, void *stream)
 {
     if (!y_branch || !y_twin || !scaling || !out || !loss || !workspace || n == 0 ||
-        !aligned16(y_branch) || !aligned16(y_twin) || !aligned16(out))
+        zira::misaligned(y_branch) || zira::misaligned(y_twin) || zira::misaligned(out))
         return ZIRA_MSDA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int grid = rsb_grid(n);
@@ -198,8 +193,8 @@ int zira_rsb_bwd_f32(const float *y_branch, const float *y_twin, const float *sc
                      float *g_twin, float *g_scaling, float *workspace, void *stream)
 {
     if (!y_branch || !y_twin || !scaling || !g_branch || !g_twin || !g_scaling || !workspace ||
-        n == 0 || !aligned16(y_branch) || !aligned16(y_twin) || !aligned16(g_branch) ||
-        !aligned16(g_twin) || (grad_out && !aligned16(grad_out)))
+        n == 0 || zira::misaligned(y_branch) || zira::misaligned(y_twin) || zira::misaligned(g_branch) ||
+        zira::misaligned(g_twin) || (grad_out && zira::misaligned(grad_out)))
         return ZIRA_MSDA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int grid = rsb_grid(n);

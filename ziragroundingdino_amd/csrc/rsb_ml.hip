@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include "lane_sum.h"
+#include "launch.h"
 #include "zira_rsb_ml.h"
 
 namespace {
@@ -457,7 +458,7 @@ inline bool make_geom(int B, int C, int HW, int G, Geom &g)
     return true;
 }
 
-inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+using zira::misaligned;
 
 }  // namespace
 

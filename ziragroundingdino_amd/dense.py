@@ -770,3 +770,22 @@ class LayerNorm(torch.nn.LayerNorm):
         if self.fused:
             return add_layer_norm(x, res, self.normalized_shape, self.weight, self.bias, self.eps)
         return super().forward(x + res)
+
+
+def _zeroed_once(cache, key, count, dtype, minimum, who):
+    """``count`` elements of ``dtype`` (at least ``minimum`` when allocated) on device ``key`` from the caller's own ``cache``:
+    allocated ZEROED once, outside any capture -- the kernels that draw tickets from it leave it at zero again, so neither a
+    later call nor a graph replay clears it.  One buffer serves one stream at a time: an eager call on another stream than the
+    last one first waits for that stream.  ``who`` opens the error of a capture that finds no buffer (it takes the device)."""
+    held = cache.get(key)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if held is None or held[0].numel() < count:
+        if capturing:
+            raise RuntimeError((who + " yet; run once outside the capture first") % (key,))
+        held = cache[key] = [torch.zeros(max(count, minimum), dtype=dtype, device=key), None]
+    if not capturing:
+        stream = torch.cuda.current_stream(key)
+        if held[1] is not None and held[1] != stream:
+            stream.wait_stream(held[1])
+        held[1] = stream
+    return held[0]

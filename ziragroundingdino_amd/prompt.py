@@ -28,6 +28,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from .dense import _zeroed_once
 
 FORCE_REFERENCE = False      # True: every call is substitute_reference
 MAX_B, MAX_T, MAX_D = (_lib.PROMPT_CONSTANTS[k] for k in ("ZIRA_PROMPT_MAX_B", "ZIRA_PROMPT_MAX_T", "ZIRA_PROMPT_MAX_D"))
@@ -86,20 +87,8 @@ class PromptTable:
         """``memory_loss``'s forward workspace (ticket word + the blocks' doubles) on ``device``: allocated ZEROED once, outside
         any capture -- the kernel leaves the ticket at zero again, so neither a later call nor a graph replay clears it.  One
         workspace serves one stream at a time: an eager call on another stream than the last one first waits for that stream."""
-        device = torch.device(device)
-        held = self._workspace.get(device)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if held is None or held[0].numel() < nbytes:
-            if capturing:
-                raise RuntimeError("prompt.memory_loss: the table has no workspace on %s yet; run once outside the capture first"
-                                   % (device,))
-            held = self._workspace[device] = [torch.zeros(nbytes, dtype=torch.uint8, device=device), None]
-        if not capturing:
-            stream = torch.cuda.current_stream(device)
-            if held[1] is not None and held[1] != stream:
-                stream.wait_stream(held[1])
-            held[1] = stream
-        return held[0]
+        return _zeroed_once(self._workspace, torch.device(device), nbytes, torch.uint8, 0,
+                            "prompt.memory_loss: the table has no workspace on %s")
 
 
 def build_table(names_list, cate_to_token_mask_list, pool_keys: Sequence[str], pool_rows: Sequence[int], T: int) -> PromptTable:

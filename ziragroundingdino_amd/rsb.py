@@ -32,7 +32,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .dense import _scratch, conv2d_as_gemm, conv2d_pair_as_gemm
+from .dense import _scratch, _zeroed_once, conv2d_as_gemm, conv2d_pair_as_gemm
 
 zero_value = 1e-8
 lan_scale = 0.1
@@ -187,21 +187,8 @@ def lora_reference(x: Tensor, w_down: Tensor, w_up: Tensor, w_twin: Tensor, scal
 
 
 def _lora_tickets(dev, words):
-    """The forward's ticket words on ``dev``: allocated ZEROED once, outside any capture -- every forward leaves them at zero
-    again, so neither a later call nor a graph replay clears them.  One buffer serves one stream at a time: an eager call on
-    another stream than the last one first waits for that stream."""
-    held = _LORA_TICKETS.get(dev)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if held is None or held[0].numel() < words:
-        if capturing:
-            raise RuntimeError("rsb.lora_apply: no ticket words on %s yet; run once outside the capture first" % (dev,))
-        held = _LORA_TICKETS[dev] = [torch.zeros(max(words, LORA_MAX_ROWS // 32 + 4), dtype=torch.int32, device=dev), None]
-    if not capturing:
-        stream = torch.cuda.current_stream(dev)
-        if held[1] is not None and held[1] != stream:
-            stream.wait_stream(held[1])
-        held[1] = stream
-    return held[0]
+    """The forward's ticket words on ``dev`` (``dense._zeroed_once``)."""
+    return _zeroed_once(_LORA_TICKETS, dev, words, torch.int32, LORA_MAX_ROWS // 32 + 4, "rsb.lora_apply: no ticket words on %s")
 
 
 def lora_native_supported(x: Tensor, w_down: Tensor, w_up: Tensor, w_twin: Tensor, scaling: Tensor) -> bool:
